@@ -18,10 +18,20 @@ per-rank counts are all-gathered, then exactly the valid records move point-to-p
 (sac_maritime_ast_amd/shard.py).
 
 Timing: W warm-up steps (at least 8 launches: the env population starts synchronised and needs
-~40 000 steps to reach the steady state of desynchronised episodes), then K timed steps in
-whole launches (at least 3), bracketed by barrier + synchronize, max over ranks.  A "step" is one
-env step of every env; with --steps below 3 launches the used count is reported beside the
-requested one.
+~40 000 steps to reach the steady state of desynchronised episodes), then exactly --steps timed
+steps (whole launches of --chunk steps and one shorter launch for the remainder), bracketed by
+barrier + synchronize, max over ranks.  A "step" is one env step of every env; ms_per_step is the
+timed wall time per timed step.
+
+A plain run does only that: set-up, warm-up, the timed steps, the result line.  --full adds what
+the record runs report beside the headline, each a measurement of its own: the config C5 line, C3
+in float64, C5 with the PyTorch-ROCm actor, and the CPU baselines.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (the last row of the
+last launch's next_state, reward, done, status and action, its per-step done counts, and the
+replay transitions of a fixed set of envs in a canonical order) as DIR/<name>.npy, so that two
+builds can be compared output for output: scenario, seeds and launch sequence depend on the
+arguments only.
 """
 from __future__ import annotations
 
@@ -47,10 +57,16 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20000)
+    ap.add_argument("--steps", type=int, default=120000,
+                    help="timed steps, exactly (default: three launches of the default --chunk)")
     ap.add_argument("--warmup", type=int, default=40000, help="steps before timing (the env population "
                     "starts synchronised; ~40k steps reach the steady state of desynchronised episodes)")
-    ap.add_argument("--min-launches", type=int, default=3, help="timed launches at least")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary lines (config C5, C3 in float64, C5 with the PyTorch-ROCm "
+                         "actor) and the CPU baselines; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--min-launches", type=int, default=3, help="--dry-run: launches at least")
     ap.add_argument("--min-warmup-launches", type=int, default=8, help="warm-up launches at least")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/collective self-check without a GPU (gloo, CPU tensors, synthetic records)")
@@ -76,12 +92,12 @@ def parse():
                     help="CPU work per baseline process (the whole leg takes ~2 s more for the imports)")
     ap.add_argument("--cpu-baseline-workers", type=int, default=16,
                     help="single-threaded oracle processes (the GPU box's CPU share is 16 cores per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-gather", action="store_true",
                     help="skip the replay-transition stream (by default every rank, N = 1 included, writes "
                          "its sampling events' transitions and the learner gathers them)")
     ap.add_argument("--launch-trace", action="store_true", help="print every launch's kernel ms to stderr")
-    ap.add_argument("--no-c5", action="store_true", help="rollout mode: skip the config C5 (policy) line")
+    ap.add_argument("--no-c5", action="store_true", help="--full, rollout mode: skip the config C5 (policy) line")
     ap.add_argument("--c5-steps", type=int, default=32 * 16 * 16, help="timed steps of the C5 line")
     ap.add_argument("--c5-warmup", type=int, default=32 * 16 * 60, help="warm-up steps of the C5 line")
     ap.add_argument("--c5-groups", type=int, default=1, help="C5 line: stream groups (1 measured fastest)")
@@ -90,7 +106,7 @@ def parse():
                          "end, so the idle share depends on the launch length against the events' spacing: K = 64 / 72 / "
                          "76 / 80 / 84 / 96 measured 1.57 / 1.66 / 1.56 / 1.66 / 1.64 / 1.53e10, DESIGN.md §9)")
     ap.add_argument("--no-extra-lines", action="store_true",
-                    help="rollout mode: skip the secondary lines (C3 in float64, C5 with the PyTorch-ROCm actor)")
+                    help="--full, rollout mode: skip the secondary lines (C3 in float64, C5 with the PyTorch-ROCm actor)")
     ap.add_argument("--trajectory-stride", type=int, default=0,
                     help="rollout mode: also gather every S-th step's trajectory rows (next_state, reward, done, "
                          "status) of every rank to rank 0 per launch (shard.TrajectoryGather; 0 = off)")
@@ -100,6 +116,8 @@ def parse():
                     help="policy mode: the actor forward in PyTorch-ROCm on the request queue (north_star's C5 "
                          "wording) instead of the fused HIP actor")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1, --warmup at least 0")
     if args.chunk is None:
         args.chunk = 32 if args.mode == "policy" else 40000
     return args
@@ -356,11 +374,56 @@ def roofline_valu(kern_ms, pmc, n_env, chunk):
 
 
 def launch_plan(args, chunk):
-    """(timed steps, warm-up steps) in whole launches: >= min_launches timed, >= the requested
-    steps; warm-up >= min_warmup_launches and >= the requested warm-up."""
-    steps = max(args.min_launches * chunk, -(-args.steps // chunk) * chunk)
+    """(lengths of the timed launches, warm-up steps).  The timed launches add up to exactly the
+    requested steps: whole launches of `chunk` steps, then one shorter launch for the remainder.
+    The warm-up runs whole launches: >= min_warmup_launches and >= the requested warm-up."""
+    n_full, tail = divmod(args.steps, chunk)
     warm = max(args.min_warmup_launches * chunk, -(-args.warmup // chunk) * chunk)
-    return steps, warm
+    return [chunk] * n_full + ([tail] if tail else []), warm
+
+
+# outputs with one row per step of a launch (env.rollout: [K, n_env, ...], done_count [K])
+ROW_OUTPUTS = ("next_state", "reward", "done", "status", "action", "done_count")
+DUMP_ARRAY_BYTES = 2 << 20     # per dumped array; ten arrays at most, each with a float64 mask at worst: < 64 MB
+DUMP_TRANSITION_ENVS = 256     # the transitions of the shard's first envs are dumped
+
+
+def _sample_rows(a, itemsize):
+    """`a` whole if it fits DUMP_ARRAY_BYTES as written, else a fixed (seeded) sample of its rows, in order."""
+    if a.dim() == 0 or a.numel() * itemsize <= DUMP_ARRAY_BYTES:
+        return a
+    row = a.numel() // a.shape[0] * itemsize
+    idx = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, DUMP_ARRAY_BYTES // row), replace=False))
+    return a[torch.as_tensor(idx, device=a.device)]
+
+
+def dump_outputs(path, arrays, rank, world):
+    """Write {name: tensor} as path/<name>.npy (path/<name>_rank<r>.npy at N > 1): reals in their
+    own precision, everything else (flags, counts, status words) as float64.  Every file holds finite
+    numbers, so that two dumps compare by plain differences: an array with non-finite entries (the
+    action's scoping angle is NaN on a step that draws none) is written with 0 in their place, beside
+    <name>_nonfinite.npy, which holds 1 where they were."""
+    os.makedirs(path, exist_ok=True)
+    suffix = (f"_rank{rank}" if world > 1 else "") + ".npy"
+    for name, t in arrays.items():
+        wide = not (t.is_floating_point() and t.dtype == torch.float32)
+        a = _sample_rows(t, 8 if wide else 4).detach().cpu().numpy()
+        a = a.astype(np.float64 if wide else np.float32)
+        bad = ~np.isfinite(a)
+        if bad.any():
+            np.save(os.path.join(path, name + "_nonfinite" + suffix), bad.astype(np.float64))
+            a = np.where(bad, a.dtype.type(0), a)
+        np.save(os.path.join(path, name + suffix), a)
+
+
+def canonical_transitions(records, count, first_env):
+    """The valid transition records of envs first_env .. first_env + DUMP_TRANSITION_ENVS - 1, sorted
+    by every column (env id first): the kernel appends records in the order its waves reach the
+    counter, which is no property of the outputs."""
+    rec = records[:count]
+    rec = rec[(rec[:, 23] >= first_env) & (rec[:, 23] < first_env + DUMP_TRANSITION_ENVS)].cpu().numpy()
+    order = np.lexsort(tuple(rec[:, c] for c in list(range(22, -1, -1)) + [23]))
+    return torch.from_numpy(rec[order])
 
 
 def bench_rollout(args, rank, world, dev):
@@ -375,11 +438,8 @@ def bench_rollout(args, rank, world, dev):
     env.reset()
     env.init_step()
     chunk = args.chunk if args.mode == "rollout" else 1
-    if args.mode == "step":
-        steps = max(args.min_launches, args.steps)
-        warm = max(args.min_warmup_launches, args.warmup)
-    else:
-        steps, warm = launch_plan(args, chunk)
+    steps = args.steps
+    lens, warm = launch_plan(args, chunk)      # step mode: chunk = 1, one launch per step
     stream = torch.cuda.current_stream(dev)
     # replay transitions of sampling events, written by the kernel with a device-side count and
     # gathered to the learner (rank 0) per launch.  Capacity per rank and launch: the measured
@@ -395,6 +455,7 @@ def bench_rollout(args, rank, world, dev):
     tgather = (TrajectoryGather(chunk, n_env, args.trajectory_stride, env.dtype, dev, world)
                if args.mode == "rollout" and getattr(args, "trajectory_stride", 0) > 0 else None)
     out = {}
+    last = {}      # the last launch's length and output dict (--dump-outputs)
     launch_no = [0]
 
     if args.mode == "step":   # one sit_step launch per env step, explicit (precomputed) random IWs
@@ -408,24 +469,28 @@ def bench_rollout(args, rank, world, dev):
                 torch.empty(n_env, dtype=torch.uint8, device=dev), torch.empty(n_env, dtype=torch.int32, device=dev),
                 torch.zeros(1, dtype=torch.int32, device=dev)]
 
-        def one(ev_pair=None):
+        def one(ev_pair=None, k=1):
             if ev_pair:
                 ev_pair[0].record(stream)
             env._call("sit_step", act.data_ptr(), sac.data_ptr(), init.data_ptr(), *[b.data_ptr() for b in bufs],
                       env._stream())
             if ev_pair:
                 ev_pair[1].record(stream)
+        last.update(k=1, out={f: b[None] for f, b in zip(("next_state", "reward", "done", "status"), bufs)})
     else:
-        def one(ev_pair=None):
+        def one(ev_pair=None, k=chunk):
             i = launch_no[0]
             if gather:     # this launch's slot of the pipelined transition gather
                 out["transitions"], out["transition_count"] = gather.buffers(i)
+            # the shorter last launch writes the first k rows of the same output buffers
+            o = out if k == chunk else {f: (t[:k] if f in ROW_OUTPUTS else t) for f, t in out.items()}
             if ev_pair:
                 ev_pair[0].record(stream)
-            env.rollout(chunk, seed=args.seed, env_id_offset=offset, out=out,
+            env.rollout(k, seed=args.seed, env_id_offset=offset, out=o,
                         transition_capacity=tcap if gather else 0)
             if ev_pair:
                 ev_pair[1].record(stream)
+            last.update(k=k, out=o)
             if gather:     # counts now, the valid records once this launch's counts are on the host
                 gather.start(i)
                 gather.progress(i - 1)
@@ -441,12 +506,12 @@ def bench_rollout(args, rank, world, dev):
         tgather.wait()
     gathered0, dropped0 = (gather.gathered, gather.dropped()) if gather else (0, 0)
     tbytes0 = tgather.bytes_moved if tgather else 0
-    n_launch = steps // chunk
+    n_launch = len(lens)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_launch)]
 
     def run():
         for i in range(n_launch):
-            one(ev[i])
+            one(ev[i], lens[i])
         if gather:
             gather.finish()
         if tgather:
@@ -455,17 +520,22 @@ def bench_rollout(args, rank, world, dev):
     launch_ms = [a.elapsed_time(b) for a, b in ev]
     if args.launch_trace:
         print("launch_ms " + " ".join(f"{x:.4f}" for x in launch_ms), file=sys.stderr)
-    kern_ms = float(np.median(launch_ms))
+    # the roofline describes the whole launches (the remainder launch only when there is no other)
+    k_roof = lens[0]
+    roof_ms = [ms for ms, k in zip(launch_ms, lens) if k == k_roof]
+    kern_ms = float(np.median(roof_ms))
     st = env.get_state()
     rs = 4 if args.precision == 32 else 8
-    alg = algorithmic_bytes_per_launch(n_env, chunk, rs, float(st["n_wpt"][1].double().mean().item()),
+    alg = algorithmic_bytes_per_launch(n_env, k_roof, rs, float(st["n_wpt"][1].double().mean().item()),
                                        float(st["n_wpt"][0].double().mean().item()), args.mode)
     env_steps = world * n_env * steps
-    pmc = latest_pmc(args.precision, args.mode, n_env, chunk)
+    pmc = latest_pmc(args.precision, args.mode, n_env, k_roof)
     rl = roofline(alg, kern_ms, pmc, kernel_name(env))
-    rl["algorithmic_bytes_per_env_step"] = alg / (n_env * chunk)
-    rl["launch_ms"] = stats_of(launch_ms)
-    rl["kernel_ms_statistic"] = "median over the timed launches (HIP events on the launch stream)"
+    rl["algorithmic_bytes_per_env_step"] = alg / (n_env * k_roof)
+    rl["launch_ms"] = stats_of(roof_ms)
+    rl["steps_per_launch"] = k_roof
+    rl["kernel_ms_statistic"] = (f"median over the timed launches of {k_roof} steps (HIP events on the launch "
+                                 f"stream)")
     if args.mode == "step":
         workload = (f"drop-in sit_step: one MultiShipRLEnv.step launch per env step for {n_env} envs "
                     f"({2 * n_env} ships), explicit IW actions, no auto-reset")
@@ -477,12 +547,26 @@ def bench_rollout(args, rank, world, dev):
     res = {
         "value": env_steps / elapsed, "steps": steps, "warmup": warm, "ms_per_step": elapsed * 1e3 / steps,
         "config": {"workload": workload, "envs_per_gpu": n_env, "ships_per_gpu": 2 * n_env,
-                   "fused_steps_per_launch": chunk, "n_launch": n_launch, "mode": args.mode,
+                   "fused_steps_per_launch": chunk, "n_launch": n_launch, "last_launch_steps": lens[-1],
+                   "mode": args.mode,
                    "parallelism": f"env-shard x{world}", "ship_steps_per_s": 2 * env_steps / elapsed,
                    "steps_requested": args.steps, "warmup_requested": args.warmup},
         "roofline": rl,
-        "roofline_valu": roofline_valu(kern_ms, pmc, n_env, chunk) if args.mode == "rollout" else None,
+        "roofline_valu": roofline_valu(kern_ms, pmc, n_env, k_roof) if args.mode == "rollout" else None,
     }
+    if args.dump_outputs:
+        # what the last timed launch returned, at its last step; records beyond the capacity are dropped in
+        # the order the waves arrive, so a launch that dropped some has no canonical record set
+        k, o = last["k"], last["out"]
+        dump = {f: o[f][k - 1] for f in ("next_state", "reward", "done", "status", "action") if f in o}
+        if "done_count" in o:
+            dump["done_count"] = o["done_count"][:k]
+        if gather is not None:
+            count = int(o["transition_count"].item())
+            dump["transition_count"] = o["transition_count"]
+            if count <= tcap:
+                dump["transitions"] = canonical_transitions(o["transitions"], count, offset)
+        res["outputs"] = dump
     if tgather is not None:
         res["config"]["rccl_trajectory_gather"] = {
             "to": "rank 0", "stride": args.trajectory_stride, "rows_per_launch_per_rank": tgather.rows,
@@ -625,8 +709,12 @@ def bench_policy(args, rank, world, dev):
             "to": "rank 0 (learner)", "records_gathered": int(stats[0].item()), "records_dropped": int(stats[1].item()),
             "capacity_per_group_replay": tcap, "pipelining": "per group: count all-gather behind each graph replay; "
                                                             "valid records point-to-point once the next replay is enqueued"}
-    return {"value": env_steps / elapsed, "steps": n_launch * chunk, "warmup": n_warm * per_graph * chunk,
-            "ms_per_step": elapsed * 1e3 / (n_launch * chunk), "config": cfg, "roofline": rl}
+    res = {"value": env_steps / elapsed, "steps": n_launch * chunk, "warmup": n_warm * per_graph * chunk,
+           "ms_per_step": elapsed * 1e3 / (n_launch * chunk), "config": cfg, "roofline": rl}
+    if args.dump_outputs:      # every group's rows of the last step of the last timed replay
+        res["outputs"] = {f"{f}_group{g}": sm.out[f][-1] for g, sm in enumerate(samplers)
+                          for f in ("next_state", "reward", "done", "status", "action")}
+    return res
 
 
 def main():
@@ -642,21 +730,25 @@ def main():
             torch.distributed.destroy_process_group()
         return
     r = bench_policy(args, rank, world, dev) if args.mode == "policy" else bench_rollout(args, rank, world, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r.pop("outputs"), rank, world)
+    # everything below the headline is a measurement of its own and runs with --full only
+    secondary = argparse.Namespace(**dict(vars(args), dump_outputs=None))
     c5 = None
-    if args.mode == "rollout" and not args.no_c5:
+    if args.full and args.mode == "rollout" and not args.no_c5:
         # config C5 beside the headline C3/C4 line: policy mode, driver-timed in the same run
-        a5 = argparse.Namespace(**vars(args))
+        a5 = argparse.Namespace(**vars(secondary))
         a5.mode, a5.chunk, a5.groups = "policy", args.c5_chunk, args.c5_groups
         a5.steps, a5.warmup = max(args.c5_steps, a5.chunk * 16 * 2), args.c5_warmup
         c5 = bench_policy(a5, rank, world, dev)
     extra = {}
     # (single-GPU runs only: the scaling runs time the headline and the C5 line; the secondary lines
     # would add two more sharded phases per N without adding a scaling measurement)
-    if args.mode == "rollout" and not args.no_extra_lines and args.precision == 32 and world == 1:
+    if args.full and args.mode == "rollout" and not args.no_extra_lines and args.precision == 32 and world == 1:
         # secondary lines (not the headline): C3 in the reference's own float64 arithmetic, and C5 with the
         # actor forward in PyTorch-ROCm on the request queue, on a HIP stream of its own (north_star's C5
         # wording); one group of 64-step launches (tools/c5_torch_sweep.sh, profiles/r06_c5_torch_sweep.json)
-        a64 = argparse.Namespace(**vars(args))
+        a64 = argparse.Namespace(**vars(secondary))
         a64.precision, a64.chunk, a64.steps, a64.warmup = 64, 10000, 30000, 40000
         r64 = bench_rollout(a64, rank, world, dev)
         extra["c3_f64"] = {"metric": "env-steps/sec, 65 536 ships per GPU, float64 (the reference's arithmetic)",
@@ -664,7 +756,7 @@ def main():
                            "warmup": r64["warmup"], "ms_per_step": r64["ms_per_step"], "config": r64["config"],
                            "roofline": r64["roofline"]}
         if not args.no_c5:
-            at = argparse.Namespace(**vars(args))
+            at = argparse.Namespace(**vars(secondary))
             at.mode, at.chunk, at.groups, at.serve, at.torch_actor, at.actor_stream = "policy", 80, 1, "queue", True, True
             at.steps, at.warmup = 80 * 16 * 8, 80 * 16 * 12
             rt = bench_policy(at, rank, world, dev)
@@ -684,7 +776,7 @@ def main():
                         "unit": "env-steps/s", "steps": c5["steps"], "warmup": c5["warmup"],
                         "ms_per_step": c5["ms_per_step"], "config": c5["config"], "roofline": c5["roofline"]}
     result.update(extra)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, args.seed, args.cpu_baseline_workers)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -60,8 +60,55 @@ def test_bench_rejects_gpus_world_size_mismatch():
 
 
 def test_launch_plan_whole_launches():
+    """The timed launches add up to exactly --steps (whole launches, then the remainder); the warm-up
+    stays whole launches, at least min_warmup_launches."""
     import argparse
     a = argparse.Namespace(steps=20, warmup=5, min_launches=3, min_warmup_launches=8)
-    assert bench.launch_plan(a, 5000) == (15000, 40000)
+    assert bench.launch_plan(a, 5000) == ([20], 40000)
     a = argparse.Namespace(steps=20001, warmup=45000, min_launches=3, min_warmup_launches=8)
-    assert bench.launch_plan(a, 5000) == (25000, 45000)
+    assert bench.launch_plan(a, 5000) == ([5000] * 4 + [1], 45000)
+    a = argparse.Namespace(steps=15000, warmup=45001, min_launches=3, min_warmup_launches=8)
+    assert bench.launch_plan(a, 5000) == ([5000] * 3, 50000)
+    a = argparse.Namespace(steps=7, warmup=0, min_launches=3, min_warmup_launches=8)
+    assert bench.launch_plan(a, 1) == ([1] * 7, 8)          # step mode: one launch per step
+
+
+def test_dump_outputs_formats(tmp_path):
+    """--dump-outputs: reals keep their precision, flags / counts / status words become float64, an
+    array above the per-array limit is a fixed sample of its rows, ranks get their own files."""
+    import numpy as np
+    import torch
+    big = torch.arange(3 * (bench.DUMP_ARRAY_BYTES // 8), dtype=torch.float32).reshape(-1, 2)
+    arrays = {"next_state": torch.arange(20, dtype=torch.float32).reshape(2, 10), "reward": torch.ones(2, dtype=torch.float64),
+              "done": torch.tensor([0, 1], dtype=torch.uint8), "status": torch.tensor([-2 ** 31, 5], dtype=torch.int32),
+              "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, 0, 1)
+    got = {f: np.load(tmp_path / "a" / f"{f}.npy") for f in arrays}
+    assert got["next_state"].dtype == np.float32 and got["reward"].dtype == np.float64
+    assert got["done"].dtype == np.float64 and got["done"].tolist() == [0.0, 1.0]
+    assert got["status"].dtype == np.float64 and got["status"].tolist() == [-2.0 ** 31, 5.0]
+    assert got["big"].nbytes <= bench.DUMP_ARRAY_BYTES and got["big"].shape[1] == 2
+    assert np.all(np.diff(got["big"][:, 0]) > 0)                          # rows of `big`, in order
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))   # the same sample every time
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(f"{f}.npy" for f in arrays)
+    # non-finite entries: 0 in the array, 1 in the mask beside it; ranks get their own files
+    act = torch.tensor([[1.0, float("nan")], [float("inf"), 2.0]], dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "c"), {"action": act}, 1, 2)
+    assert np.load(tmp_path / "c" / "action_rank1.npy").tolist() == [[1.0, 0.0], [0.0, 2.0]]
+    assert np.load(tmp_path / "c" / "action_nonfinite_rank1.npy").tolist() == [[0.0, 1.0], [1.0, 0.0]]
+
+
+def test_canonical_transitions_order_free():
+    """The dumped transition records do not depend on the order the kernel appended them in."""
+    import torch
+    g = torch.Generator().manual_seed(3)
+    rec = torch.rand(500, 24, generator=g, dtype=torch.float64)
+    rec[:, 23] = torch.randint(1000, 1000 + 2 * bench.DUMP_TRANSITION_ENVS, (500,), generator=g).double()
+    rec[40:, 23] = rec[:460, 23]                                           # several records per env
+    a = bench.canonical_transitions(rec, 480, 1000)
+    perm = torch.randperm(480, generator=g)
+    b = bench.canonical_transitions(torch.cat([rec[:480][perm], rec[480:]]), 480, 1000)
+    assert torch.equal(a, b) and 0 < a.shape[0] < 480
+    assert bool((a[:, 23] < 1000 + bench.DUMP_TRANSITION_ENVS).all()) and bool((a[1:, 23] >= a[:-1, 23]).all())
+    assert bench.canonical_transitions(rec, 0, 1000).shape == (0, 24)

@@ -21,7 +21,7 @@ a)
   tools/gpu_steps.sh \
     $T/smoke 200 python3 -u -c "import __graft_entry__ as g; g.smoke()" --- \
     $T/tests 900 env SIT_TEST_RECORD_DIR=$O python3 -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -s --- \
-    $T/bench 400 python3 -u bench.py || exit $?
+    $T/bench 400 python3 -u bench.py --full || exit $?
   bash $0 $T p ;;
 p)
   # rocprofv3 kernel stats + the step kernel's dispatches (timed-launch averages) of each line's launch shape

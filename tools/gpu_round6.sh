@@ -44,7 +44,7 @@ c)
   tools/gpu_steps.sh \
     $T/tests 900 env SIT_TEST_RECORD_DIR=$O python3 -u -m pytest tests/test_gpu_parity.py tests/test_gpu_compat.py -m gpu -v \
       --timeout 600 --timeout-method thread -s -k "fast_trig or free_running_within or float32_attribute or launch_partition" --- \
-    $T/bench 300 python3 -u bench.py --- \
+    $T/bench 300 python3 -u bench.py --full --- \
     $T/torch_sweep 600 bash tools/c5_torch_sweep.sh $O/c5t 1:64:3:1 1:64:6:1 1:64:8:1 1:80:4:1 1:64:4:1 ;;
 d)
   tools/gpu_steps.sh \

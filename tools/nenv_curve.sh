@@ -7,7 +7,7 @@ out=$1
 mkdir -p $out
 for n in 8192 16384 24576 32768 49152 65536 98304 131072; do
   timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-c5 --no-extra-lines --n-env $n --chunk 20000 \
-    --steps 40000 --warmup 40000 > $out/n$n.json 2> $out/n$n.err || { echo "n=$n failed"; tail -3 $out/n$n.err; exit 1; }
+    --steps 60000 --warmup 40000 > $out/n$n.json 2> $out/n$n.err || { echo "n=$n failed"; tail -3 $out/n$n.err; exit 1; }
   python3 - $out/n$n.json $n <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
