@@ -452,6 +452,62 @@ int sit_state_bytes(const sit_handle* h, size_t* bytes);
 int sit_get_state(sit_handle* h, void* dst, void* stream);
 int sit_set_state(sit_handle* h, const void* src, void* stream);
 
+/* ---- episode records (device-side episode reducer) ---------------------------------
+ * What the reference's driver loop keeps per episode (test_beds/main_ast.py:310-440: episode_reward,
+ * episode_steps, status, action_record[i_episode]), reduced on the device from the [n_steps][n_env]
+ * rows a sit_rollout or sit_step has just written: a post-pass on the same stream (three kernels),
+ * for rows of any producer and mode.  The handle owns one accumulator: per env the running values
+ * below, kept across updates, and rows_seen (int64), the rows consumed by earlier updates.
+ *
+ * An update reads rows k = 0..n_steps-1 of every env e in row order:
+ *  - a row whose status has SIT_ST_NO_STEP is skipped entirely (reward not read into the sum, even if
+ *    NaN; done ignored);
+ *  - ret (float64) = ret + (double)reward[k][e]: one IEEE add per row, for both precisions (the
+ *    reference's episode_reward += reward); steps counts the rows stepped in the episode; events
+ *    counts the rows whose action_out[k][e][3] != 0; angle[j] = action_out[k][e][2] of event j for
+ *    j < SIT_EPISODE_ACTIONS (later events are counted, not stored); episode counts the episodes
+ *    this accumulator has finished for env e;
+ *  - a row with done != 0 ends the episode: one record is emitted and ret, steps, events and the
+ *    angles start again from zero / NaN.
+ * Record: double[SIT_EPISODE_DIM], integers as exactly representable doubles:
+ *   [0] global env id (env_id_offset + e)   [1] episode number of that env (0-based)   [2] steps
+ *   [3] return (ret after the done row)     [4] terminal status bits (the done row's status, uint32)
+ *   [5] events                              [6] row index of the done row (rows_seen + k)
+ *   [7] terminal reward                     [8:18] the done row's next_state (NaN without next_state)
+ *   [18:32] angle[0..13], NaN-padded (all NaN without action_out)
+ * The records of one update are appended at *record_count in ascending (env id, episode) order; the
+ * slot of a record is a function of the inputs only, never of scheduling.  Records past
+ * record_capacity are counted in *record_count but not written.  status_hist[b] += 1 for every
+ * finished episode (written or not) whose terminal status has bit b.
+ *
+ * sit_episodes_reset allocates the accumulator and every scratch buffer on first use and zeroes all
+ * running values and rows_seen; the first sit_episodes_update does the same if reset was never
+ * called.  Afterwards an update allocates nothing and never synchronises, so it can be captured in a
+ * HIP graph: call reset once before capturing.  The accumulator is freed by sit_destroy and is not
+ * part of the sit_get_state blob; sit_episodes_get / _set copy it (sit_episodes_bytes bytes, device
+ * pointers) for checkpointing. */
+#define SIT_EPISODE_ACTIONS 14
+#define SIT_EPISODE_DIM 32
+typedef struct sit_episodes_args {
+  int32_t n_steps;
+  int32_t record_capacity;
+  int64_t env_id_offset;
+  const void* reward;       /* real[n_steps][n_env]        required */
+  const uint8_t* done;      /* u8[n_steps][n_env]          required */
+  const uint32_t* status;   /* u32[n_steps][n_env]         required */
+  const void* action_out;   /* real[n_steps][n_env][4]     or NULL  */
+  const void* next_state;   /* real[n_steps][n_env][10]    or NULL  */
+  double* records;          /* double[record_capacity][32] or NULL  */
+  int64_t* record_count;    /* int64[1]: += finished episodes (written or not); required */
+  int64_t* status_hist;     /* int64[32] or NULL */
+} sit_episodes_args;
+size_t sit_episodes_args_size(void);
+int sit_episodes_reset(sit_handle* h, void* stream);
+int sit_episodes_update(sit_handle* h, const sit_episodes_args* a, void* stream);
+int sit_episodes_bytes(const sit_handle* h, size_t* bytes);
+int sit_episodes_get(sit_handle* h, void* dst, void* stream);
+int sit_episodes_set(sit_handle* h, const void* src, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,9 +4,10 @@ from . import _lib
 from .config import params, params_from_reference
 from .scenario import Scenario, make_scenario
 from .status import status_string
+from .episodes import EpisodeLog, episodes_reference
 
 __all__ = ["params", "params_from_reference", "Scenario", "make_scenario", "status_string",
-           "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library"]
+           "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library", "EpisodeLog", "episodes_reference"]
 
 
 def load_library():

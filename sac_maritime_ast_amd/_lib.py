@@ -22,6 +22,7 @@ SIT_TRANSITION_DIM = 24
 SIT_ACTOR_HIDDEN = 256
 SIT_ACTOR_WEIGHTS = SIT_ACTOR_HIDDEN * SIT_OBS_DIM + SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN ** 2 + SIT_ACTOR_HIDDEN + 2 * SIT_ACTOR_HIDDEN + 2
 SIT_LOG_KEYS, SIT_LOG_ROWS = 27, 62
+SIT_EPISODE_ACTIONS, SIT_EPISODE_DIM = 14, 32
 INIT_FIELDS = ("north", "east", "yaw", "surge", "sway", "yaw_rate", "shaft_speed", "desired_speed",
                "ship_speed_i", "shaft_speed_i")
 
@@ -89,6 +90,14 @@ class RolloutArgs(ctypes.Structure):
     ]
 
 
+class EpisodesArgs(ctypes.Structure):
+    _fields_ = [
+        ("n_steps", c_int32), ("record_capacity", c_int32), ("env_id_offset", c_int64),
+        ("reward", c_void_p), ("done", c_void_p), ("status", c_void_p), ("action_out", c_void_p),
+        ("next_state", c_void_p), ("records", c_void_p), ("record_count", c_void_p), ("status_hist", c_void_p),
+    ]
+
+
 class SitError(RuntimeError):
     pass
 
@@ -132,6 +141,12 @@ SIGNATURES = {
     "sit_state_bytes": (c_int32, [c_void_p, POINTER(c_size_t)]),
     "sit_get_state": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "sit_set_state": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "sit_episodes_args_size": (c_size_t, []),
+    "sit_episodes_reset": (c_int32, [c_void_p, c_void_p]),
+    "sit_episodes_update": (c_int32, [c_void_p, POINTER(EpisodesArgs), c_void_p]),
+    "sit_episodes_bytes": (c_int32, [c_void_p, POINTER(c_size_t)]),
+    "sit_episodes_get": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "sit_episodes_set": (c_int32, [c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -160,6 +175,9 @@ def load():
     if lib.sit_rollout_args_size() != ctypes.sizeof(RolloutArgs):
         raise ImportError(f"sit_rollout_args layout mismatch: C {lib.sit_rollout_args_size()} vs "
                           f"ctypes {ctypes.sizeof(RolloutArgs)} bytes")
+    if hasattr(lib, "sit_episodes_args_size") and lib.sit_episodes_args_size() != ctypes.sizeof(EpisodesArgs):
+        raise ImportError(f"sit_episodes_args layout mismatch: C {lib.sit_episodes_args_size()} vs "
+                          f"ctypes {ctypes.sizeof(EpisodesArgs)} bytes")
     _lib = lib
     return lib
 

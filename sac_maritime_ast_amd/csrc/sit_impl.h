@@ -1329,6 +1329,7 @@ struct sit_handle {
   bool have_map = false, have_routes = false, have_init = false;
   unsigned char* stage = nullptr;       // sit_step_host: pinned coherent host staging
   unsigned char* stage_dev = nullptr;   // its device address
+  unsigned char* episodes = nullptr;    // sit_episodes_*: accumulator blob + scratch (sit_episodes.h)
 };
 
 namespace {

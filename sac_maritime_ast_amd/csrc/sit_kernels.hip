@@ -3,6 +3,7 @@
 
 #include "sit_impl.h"
 #include "sit_actor.h"
+#include "sit_episodes.h"
 
 namespace {
 
@@ -303,6 +304,7 @@ void sit_destroy(sit_handle* h) {
   if (h->blob) (void)setup_free(h->blob);
   if (h->scen) (void)setup_free(h->scen);
   if (h->map) (void)setup_free(h->map);
+  if (h->episodes) (void)setup_free(h->episodes);
 #ifndef SIT_HOST_MEMORY_TEST
   if (h->stage) (void)hipHostFree(h->stage);
 #endif
@@ -918,6 +920,61 @@ int sit_set_state(sit_handle* h, const void* src, void* stream) {
   // the cached IW terrain tests (iw_key_*) are answers for the map of the handle that saved the blob:
   // a restored state re-tests its IW against this handle's map
   HIP_TRY(h, hipMemsetAsync(h->blob + h->off[F_IWK_FLAGS], 0, (size_t)h->n_env * 4, (hipStream_t)stream));
+  return SIT_OK;
+}
+
+// ---- episode records (sit_episodes.h) ------------------------------------------------------
+size_t sit_episodes_args_size(void) { return sizeof(sit_episodes_args); }
+
+int sit_episodes_reset(sit_handle* h, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  int rc = episodes_alloc(h);
+  if (rc) return rc;
+  return episodes_launch_reset(h, (hipStream_t)stream);
+}
+
+int sit_episodes_update(sit_handle* h, const sit_episodes_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (!a) return fail(h, SIT_E_INVALID, "episodes: null args");
+  if (a->n_steps <= 0) return fail(h, SIT_E_INVALID, "episodes: n_steps must be positive (got %d)", a->n_steps);
+  if (a->record_capacity < 0)
+    return fail(h, SIT_E_INVALID, "episodes: record_capacity must be >= 0 (got %d)", a->record_capacity);
+  if (!a->reward) return fail(h, SIT_E_INVALID, "episodes: reward is required");
+  if (!a->done) return fail(h, SIT_E_INVALID, "episodes: done is required");
+  if (!a->status) return fail(h, SIT_E_INVALID, "episodes: status is required");
+  if (!a->record_count) return fail(h, SIT_E_INVALID, "episodes: record_count is required");
+  if (!a->records && a->record_capacity > 0)
+    return fail(h, SIT_E_INVALID, "episodes: records is NULL with record_capacity %d", a->record_capacity);
+  if (a->env_id_offset < 0) return fail(h, SIT_E_INVALID, "episodes: env_id_offset must be >= 0");
+  if (!h->episodes) {   // first use without sit_episodes_reset: allocate and zero (not capturable)
+    int rc = sit_episodes_reset(h, stream);
+    if (rc) return rc;
+  }
+  return h->precision == SIT_F64 ? episodes_launch_update<double>(h, a, (hipStream_t)stream)
+                                 : episodes_launch_update<float>(h, a, (hipStream_t)stream);
+}
+
+int sit_episodes_bytes(const sit_handle* h, size_t* bytes) {
+  if (!h || !bytes) return fail(nullptr, SIT_E_INVALID, "null argument");
+  *bytes = ep_layout(h).blob_bytes;
+  return SIT_OK;
+}
+
+int sit_episodes_get(sit_handle* h, void* dst, void* stream) {
+  if (!h || !dst) return fail(h, SIT_E_INVALID, "null argument");
+  if (!h->episodes) {
+    int rc = sit_episodes_reset(h, stream);
+    if (rc) return rc;
+  }
+  HIP_TRY(h, hipMemcpyAsync(dst, h->episodes, ep_layout(h).blob_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return SIT_OK;
+}
+
+int sit_episodes_set(sit_handle* h, const void* src, void* stream) {
+  if (!h || !src) return fail(h, SIT_E_INVALID, "null argument");
+  int rc = episodes_alloc(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipMemcpyAsync(h->episodes, src, ep_layout(h).blob_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SIT_OK;
 }
 

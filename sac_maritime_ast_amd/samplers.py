@@ -45,6 +45,14 @@ from torch import nn
 
 from . import _lib
 from .env import VecMultiShipRLEnv
+from .episodes import EpisodeLog
+
+# the rows an EpisodeLog reduces (samplers with episode_capacity > 0 add them to `want`)
+EPISODE_ROWS = ("reward", "done", "status", "action")
+
+
+def _want_episode_rows(want):
+    return tuple(want) + tuple(k for k in EPISODE_ROWS if k not in want)
 
 LOG_SIG_CAP_MIN, LOG_SIG_CAP_MAX = -20.0, 2.0   # ast_core/distributions/normal.py:15-16
 EPS = 1e-6                                      # ast_core/policies/gaussian_policy.py:18
@@ -164,8 +172,11 @@ class PolicySampler:
     def __init__(self, env: VecMultiShipRLEnv, policy: nn.Module, chunk: int = 32, seed: int = 25450,
                  env_id_offset: int = 0, request_capacity: int | None = None, mask_horizon: int = 600,
                  transition_capacity: int = 0, deterministic: bool = False, actor_dtype=None,
-                 fused_actor: bool = True, serve: str | None = None, actor_stream: bool = False):
+                 fused_actor: bool = True, serve: str | None = None, actor_stream: bool = False,
+                 episode_capacity: int = 0):
         self.env, self.policy, self.chunk, self.seed = env, policy, int(chunk), int(seed)
+        # episode records (episodes.EpisodeLog) of every launch, reduced on the launch's stream
+        self.episodes = EpisodeLog(env, episode_capacity, env_id_offset) if episode_capacity > 0 else None
         # queue serving: the actor on a HIP stream of its own, forked after the env launch and joined
         # before the next (north_star's "actor forward interleaved with the HIP env step on separate
         # streams"; with one group the two kernels still run in order: the next launch needs the actions)
@@ -240,6 +251,8 @@ class PolicySampler:
         if (self.serve == "kernel" and not torch.cuda.is_current_stream_capturing()
                 and self._weights_version() != self._w_version):
             self.refresh_weights()
+        if self.episodes is not None:
+            want = _want_episode_rows(want)
         if events is not None:
             events[0].record(torch.cuda.current_stream(self.env.device))
         self.env.rollout(self.chunk, seed=self.seed, env_id_offset=self.env_id_offset, out=self.out,
@@ -247,6 +260,8 @@ class PolicySampler:
                          mask_horizon=self.mask_horizon, policy_io=self.io, reset_transitions=first)
         if events is not None:
             events[1].record(torch.cuda.current_stream(self.env.device))
+        if self.episodes is not None:
+            self.episodes.update(self.out)
         if self.serve == "queue":
             if self.actor_stream is None:
                 self.act()
@@ -259,8 +274,8 @@ class PolicySampler:
         return self.out
 
     def capture(self, n_launch: int = 2, want=("next_state", "reward", "done", "status", "action")):
-        """Record `n_launch` launches (env kernel [+ admission + actor]) into one HIP graph; replay()
-        then runs them with a single submission (the per-launch host work of ctypes and ~10 torch
+        """Record `n_launch` launches (env kernel [+ episode records] [+ admission + actor]) into one HIP
+        graph; replay() then runs them with a single submission (the per-launch host work of ctypes and ~10 torch
         ops otherwise bounds short chunks).  The output buffers are those of the last launch."""
         if n_launch < 1:
             raise ValueError("capture at least one launch")
@@ -368,8 +383,10 @@ class IntermediateWaypointSampler:
     until `start_steps` env-steps, then mode 1 (policy) — main_ast.py:337-349."""
 
     def __init__(self, env: VecMultiShipRLEnv, policy: nn.Module | None = None, chunk: int = 32,
-                 seed: int = 25450, start_steps: int = 0, env_id_offset: int = 0, **kw):
+                 seed: int = 25450, start_steps: int = 0, env_id_offset: int = 0, episode_capacity: int = 0, **kw):
         self.env, self.chunk, self.seed, self.env_id_offset = env, int(chunk), int(seed), int(env_id_offset)
+        # one log for both modes (the running values live in the env's handle)
+        self.episodes = EpisodeLog(env, episode_capacity, env_id_offset) if episode_capacity > 0 else None
         self.start_steps = int(start_steps)
         self.total = 0
         self.policy_sampler = PolicySampler(env, policy, chunk, seed, env_id_offset, **kw) if policy is not None else None
@@ -378,8 +395,10 @@ class IntermediateWaypointSampler:
     def launch(self):
         if self.policy_sampler is None or self.total < self.start_steps:
             self.env.rollout(self.chunk, seed=self.seed, env_id_offset=self.env_id_offset, out=self.out)
-            self.total += self.chunk * self.env.n_env
-            return self.out
-        out = self.policy_sampler.launch()
+            out = self.out
+        else:                                  # (its default `want` holds every row the log reduces)
+            out = self.policy_sampler.launch()
         self.total += self.chunk * self.env.n_env
+        if self.episodes is not None:
+            self.episodes.update(out)
         return out
