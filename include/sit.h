@@ -508,6 +508,77 @@ int sit_episodes_bytes(const sit_handle* h, size_t* bytes);
 int sit_episodes_get(sit_handle* h, void* dst, void* stream);
 int sit_episodes_set(sit_handle* h, const void* src, void* stream);
 
+/* ---- replay memory (device-side ring and minibatches) -------------------------------
+ * What the reference's driver loop does with its ReplayMemory (test_beds/main_ast.py:350-396:
+ * memory.push per sampling event, len(memory), memory.sample for agent.update_parameters), on the
+ * transition records above.  The caller owns both tensors, so a checkpoint is those two:
+ *   ring    real[capacity][SIT_TRANSITION_DIM], 4-real aligned
+ *   cursor  int64[4] = {pushed, dropped, draws, 0}: records pushed so far (the ring holds
+ *           size = min(pushed, capacity) of them), records their source buffers had no room for,
+ *           minibatches drawn so far
+ *
+ * sit_replay_push appends the records of one source buffer (a sit_rollout's transitions and
+ * transition_count: records are counted, not clamped).  With count = max(*src_count, 0), read on the
+ * device, and n = min(count, src_capacity):
+ *  - the n valid records are taken in canonical order: ascending env id (column 23, as uint32; a value
+ *    that is no integer id in [0, 2^32 - 2) sorts behind every id), and within one env the order in
+ *    which they stand in src.  One env is always stepped by the same lane of the same wave, whose slot
+ *    allocations increase over time, so this is "env-major, each env in step order", whatever order the
+ *    waves reached the counter in;
+ *  - record j of that order goes to slot (pushed + j) mod capacity; if n > capacity only the last
+ *    capacity records are written, so no slot is written twice in one push;
+ *  - pushed += n, dropped += count - n.
+ * Pushing the buffers of ranks 0, 1, ... one after another (shard r owns ids [r n_env, (r+1) n_env))
+ * therefore leaves the ring one rank owning all envs would have.
+ *
+ * sit_replay_sample draws n_batches minibatches of batch records.  Minibatch u has draw number
+ * d = draws + u; its element b is ring row P(b mod size), P = P_{seed,d} a bijection of [0, size), so for
+ * batch <= size the rows of one minibatch are distinct (a sample without replacement):
+ *  - a 4-round balanced Feistel network on 2h bits, h = ceil(max(bit_length(size - 1), 2) / 2): with
+ *    x = L 2^h + R, a round maps (L, R) to (R, L ^ F), F the low h bits of word 0 of
+ *    Philox4x32-10(key = (seed lo, seed hi), ctr = (R, 0x525000 | round, d lo, d hi)), round = 0..3;
+ *  - applied again while the value is not below size (cycle walking).
+ * Outputs, [n_batches][batch] rows: state real[..][10], action real[..][1], reward real, next_state
+ * real[..][10], mask real (columns 0:10, 10, 11, 12:22, 22, copied as bits), env int32 (column 23; -1 if it
+ * is no id below 2^31), index int32 (the ring row).  From an empty ring every output is zero and index
+ * is -1.  Then draws += n_batches.
+ *
+ * Push runs a key kernel, a stable radix sort of (env id, source row) over src_capacity items, a
+ * scatter with 16-byte accesses and a one-thread cursor update; sample a gather kernel and a cursor
+ * update; all on the caller's stream, with no host synchronisation.  The sort's scratch belongs to the
+ * handle and is freed by sit_destroy.  sit_replay_reserve allocates it for source buffers of up to
+ * max_src_capacity records; a push that needs more grows it, which allocates and cannot be captured
+ * (the contract of sit_episodes_reset).  After a sufficient reserve, push and sample allocate nothing
+ * and can be captured in a HIP graph. */
+typedef struct sit_replay_push_args {
+  int32_t capacity;         /* ring records, > 0 */
+  int32_t src_capacity;     /* records src has room for, > 0 */
+  void* ring;               /* real[capacity][24] */
+  int64_t* cursor;          /* int64[4] */
+  const void* src;          /* real[src_capacity][24], 4-real aligned */
+  const int32_t* src_count; /* int32[1]: records counted by the producer */
+} sit_replay_push_args;
+typedef struct sit_replay_sample_args {
+  int32_t capacity;         /* ring records, > 0 */
+  int32_t batch;            /* > 0 */
+  int32_t n_batches;        /* > 0; batch * n_batches <= 2^30 */
+  uint64_t seed;
+  const void* ring;         /* real[capacity][24] */
+  int64_t* cursor;          /* int64[4] */
+  void* state;              /* real[n_batches][batch][10] */
+  void* action;             /* real[n_batches][batch][1]  */
+  void* reward;             /* real[n_batches][batch]     */
+  void* next_state;         /* real[n_batches][batch][10] */
+  void* mask;               /* real[n_batches][batch]     */
+  int32_t* env;             /* int32[n_batches][batch]    */
+  int32_t* index;           /* int32[n_batches][batch]    */
+} sit_replay_sample_args;
+size_t sit_replay_push_args_size(void);
+size_t sit_replay_sample_args_size(void);
+int sit_replay_reserve(sit_handle* h, int32_t max_src_capacity, void* stream);
+int sit_replay_push(sit_handle* h, const sit_replay_push_args* a, void* stream);
+int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

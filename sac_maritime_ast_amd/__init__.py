@@ -5,9 +5,11 @@ from .config import params, params_from_reference
 from .scenario import Scenario, make_scenario
 from .status import status_string
 from .episodes import EpisodeLog, episodes_reference
+from .replay import ReplayMemory, replay_reference
 
 __all__ = ["params", "params_from_reference", "Scenario", "make_scenario", "status_string",
-           "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library", "EpisodeLog", "episodes_reference"]
+           "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library", "EpisodeLog", "episodes_reference",
+           "ReplayMemory", "replay_reference"]
 
 
 def load_library():

@@ -98,6 +98,21 @@ class EpisodesArgs(ctypes.Structure):
     ]
 
 
+class ReplayPushArgs(ctypes.Structure):
+    _fields_ = [
+        ("capacity", c_int32), ("src_capacity", c_int32), ("ring", c_void_p), ("cursor", c_void_p),
+        ("src", c_void_p), ("src_count", c_void_p),
+    ]
+
+
+class ReplaySampleArgs(ctypes.Structure):
+    _fields_ = [
+        ("capacity", c_int32), ("batch", c_int32), ("n_batches", c_int32), ("seed", c_uint64),
+        ("ring", c_void_p), ("cursor", c_void_p), ("state", c_void_p), ("action", c_void_p), ("reward", c_void_p),
+        ("next_state", c_void_p), ("mask", c_void_p), ("env", c_void_p), ("index", c_void_p),
+    ]
+
+
 class SitError(RuntimeError):
     pass
 
@@ -147,6 +162,11 @@ SIGNATURES = {
     "sit_episodes_bytes": (c_int32, [c_void_p, POINTER(c_size_t)]),
     "sit_episodes_get": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "sit_episodes_set": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "sit_replay_push_args_size": (c_size_t, []),
+    "sit_replay_sample_args_size": (c_size_t, []),
+    "sit_replay_reserve": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "sit_replay_push": (c_int32, [c_void_p, POINTER(ReplayPushArgs), c_void_p]),
+    "sit_replay_sample": (c_int32, [c_void_p, POINTER(ReplaySampleArgs), c_void_p]),
 }
 
 _lib = None
@@ -178,6 +198,9 @@ def load():
     if hasattr(lib, "sit_episodes_args_size") and lib.sit_episodes_args_size() != ctypes.sizeof(EpisodesArgs):
         raise ImportError(f"sit_episodes_args layout mismatch: C {lib.sit_episodes_args_size()} vs "
                           f"ctypes {ctypes.sizeof(EpisodesArgs)} bytes")
+    for fn, struct in (("sit_replay_push_args_size", ReplayPushArgs), ("sit_replay_sample_args_size", ReplaySampleArgs)):
+        if hasattr(lib, fn) and getattr(lib, fn)() != ctypes.sizeof(struct):
+            raise ImportError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} vs ctypes {ctypes.sizeof(struct)} bytes")
     _lib = lib
     return lib
 

@@ -1330,6 +1330,11 @@ struct sit_handle {
   unsigned char* stage = nullptr;       // sit_step_host: pinned coherent host staging
   unsigned char* stage_dev = nullptr;   // its device address
   unsigned char* episodes = nullptr;    // sit_episodes_*: accumulator blob + scratch (sit_episodes.h)
+  unsigned char* replay = nullptr;      // sit_replay_push: sort keys, values and temporary storage (sit_replay.h)
+  size_t replay_items = 0;              //   records the scratch holds
+  size_t replay_temp = 0;               //   bytes of the sort's temporary storage
+  size_t replay_asked = 0;              //   the last size query: items and the bytes hipcub asked for
+  size_t replay_answer = 0;
 };
 
 namespace {

@@ -4,6 +4,7 @@
 #include "sit_impl.h"
 #include "sit_actor.h"
 #include "sit_episodes.h"
+#include "sit_replay.h"
 
 namespace {
 
@@ -305,6 +306,7 @@ void sit_destroy(sit_handle* h) {
   if (h->scen) (void)setup_free(h->scen);
   if (h->map) (void)setup_free(h->map);
   if (h->episodes) (void)setup_free(h->episodes);
+  if (h->replay) (void)setup_free(h->replay);
 #ifndef SIT_HOST_MEMORY_TEST
   if (h->stage) (void)hipHostFree(h->stage);
 #endif
@@ -976,6 +978,52 @@ int sit_episodes_set(sit_handle* h, const void* src, void* stream) {
   if (rc) return rc;
   HIP_TRY(h, hipMemcpyAsync(h->episodes, src, ep_layout(h).blob_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SIT_OK;
+}
+
+// ---- replay memory (sit_replay.h) ----------------------------------------------------------
+size_t sit_replay_push_args_size(void) { return sizeof(sit_replay_push_args); }
+size_t sit_replay_sample_args_size(void) { return sizeof(sit_replay_sample_args); }
+
+int sit_replay_reserve(sit_handle* h, int32_t max_src_capacity, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (max_src_capacity <= 0)
+    return fail(h, SIT_E_INVALID, "replay: max_src_capacity must be positive (got %d)", max_src_capacity);
+  return replay_reserve(h, (size_t)max_src_capacity, (hipStream_t)stream);
+}
+
+int sit_replay_push(sit_handle* h, const sit_replay_push_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (!a) return fail(h, SIT_E_INVALID, "replay: null args");
+  if (a->capacity <= 0) return fail(h, SIT_E_INVALID, "replay: capacity must be positive (got %d)", a->capacity);
+  if (a->src_capacity <= 0)
+    return fail(h, SIT_E_INVALID, "replay: src_capacity must be positive (got %d)", a->src_capacity);
+  if (!a->ring) return fail(h, SIT_E_INVALID, "replay: ring is required");
+  if (!a->cursor) return fail(h, SIT_E_INVALID, "replay: cursor is required");
+  if (!a->src) return fail(h, SIT_E_INVALID, "replay: src is required");
+  if (!a->src_count) return fail(h, SIT_E_INVALID, "replay: src_count is required");
+  const size_t quad = 4 * real_size(h);   // records are copied in 16-byte pieces
+  if ((uintptr_t)a->ring % quad) return fail(h, SIT_E_INVALID, "replay: ring must be aligned to 4 reals (%zu bytes)", quad);
+  if ((uintptr_t)a->src % quad) return fail(h, SIT_E_INVALID, "replay: src must be aligned to 4 reals (%zu bytes)", quad);
+  return h->precision == SIT_F64 ? replay_launch_push<double>(h, a, (hipStream_t)stream)
+                                 : replay_launch_push<float>(h, a, (hipStream_t)stream);
+}
+
+int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (!a) return fail(h, SIT_E_INVALID, "replay: null args");
+  if (a->capacity <= 0) return fail(h, SIT_E_INVALID, "replay: capacity must be positive (got %d)", a->capacity);
+  if (a->batch <= 0) return fail(h, SIT_E_INVALID, "replay: batch must be positive (got %d)", a->batch);
+  if (a->n_batches <= 0) return fail(h, SIT_E_INVALID, "replay: n_batches must be positive (got %d)", a->n_batches);
+  if ((int64_t)a->batch * a->n_batches > (int64_t)1 << 30)
+    return fail(h, SIT_E_INVALID, "replay: batch * n_batches must not exceed 2^30 (got %d * %d)", a->batch, a->n_batches);
+  if (!a->ring) return fail(h, SIT_E_INVALID, "replay: ring is required");
+  if (!a->cursor) return fail(h, SIT_E_INVALID, "replay: cursor is required");
+  if (!a->state || !a->action || !a->reward || !a->next_state || !a->mask || !a->env || !a->index)
+    return fail(h, SIT_E_INVALID, "replay: every output (state, action, reward, next_state, mask, env, index) is required");
+  const size_t quad = 4 * real_size(h);
+  if ((uintptr_t)a->ring % quad) return fail(h, SIT_E_INVALID, "replay: ring must be aligned to 4 reals (%zu bytes)", quad);
+  return h->precision == SIT_F64 ? replay_launch_sample<double>(h, a, (hipStream_t)stream)
+                                 : replay_launch_sample<float>(h, a, (hipStream_t)stream);
 }
 
 }  // extern "C"
