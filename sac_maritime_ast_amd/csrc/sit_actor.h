@@ -17,7 +17,7 @@
 // within 1e-5.
 #pragma once
 
-#include "sit_device.h"
+#include "sit_host.h"
 
 namespace {
 

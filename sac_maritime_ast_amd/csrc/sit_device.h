@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "sit.h"
+#include "sit_map_format.h"   // Edge<T>, kGrid, kBands, kFine, ...: the map format and its comment
 
 namespace sit {
 
@@ -175,8 +176,6 @@ constexpr int kGroups = SIT_GROUPS;
 #ifndef SIT_MIN_WAVES
 #define SIT_MIN_WAVES 1   // step kernel: waves per SIMD the register budget must allow
 #endif
-constexpr int kMaxPolyVerts = 256;
-constexpr int kMaxPolys = 32;
 
 // --------------------------------------------------------------------------------------
 // math overloads
@@ -293,45 +292,8 @@ __device__ __forceinline__ bool simpl_of(const C& c) {
   else return c.mach_simpl != 0;
 }
 
-// island map (obstacle.py:92-124): edge i of the closed rings runs from (ax, ay) to (bx, by);
-// coordinates are (x = east, y = north) as in obstacle.py:128.  One Edge record per edge (one
-// LDS base pointer, immediate field offsets) so the predicates need no per-array registers.
-//
-// Spatial index (built on the host by sit_load_map, exact by construction), one u16 array:
-//   idx[0 .. 4*G*G)          grid cell records, 8 bytes each: the list's first group inline
-//                            (x = ids 0-3, y bits 0-7 = id 4), y bits 8-15 = number of further
-//                            groups, y bits 16-31 = the first of them (in 8-byte groups from the
-//                            start of idx).  The cell's first 5 candidates are then one LDS read
-//                            away from the cell index, their edges two.
-//   idx[kBandBase ..]        NB+1 band starts (absolute positions in idx)
-//   then the band entries (edge ids), then the further grid groups (8-byte aligned).
-//  * grid: G x G cells over the map extent plus a margin; cell c lists every edge that can be
-//    the nearest edge of some point within 1 m of the cell (conservative prefilter, then a
-//    Lipschitz-sampled refinement with a 1 m float slack; sit_load_map), so the minimum over the
-//    list equals the minimum over all edges.  A list is padded to a multiple of 5 with its first
-//    id and packed as 5 u8 ids per 8-byte group, so one LDS read yields 5 ids whose edge loads
-//    are independent (duplicates do not change a minimum).
-//  * bands: NB horizontal bands; band b lists every edge whose y-range meets the band (+-1 m).
-//    GEOS's ray-crossing test only looks at edges whose y-range contains the point's y.
-//  * classes (separate u32 array): kFine x kFine cells over the map extent + 100 m, 2 bits per
-//    cell: 0 = no boundary within 1 m of the cell and its points are outside every polygon,
-//    1 = likewise inside one, 2 = mixed.  A point outside the class grid is > 100 m off the
-//    map and therefore outside every polygon.  With ~40 m cells every point farther than
-//    ~31 m from the shore resolves by one lookup.
-constexpr int kGrid = 32;
-constexpr int kBands = 64;
-constexpr int kBandBase = 4 * kGrid * kGrid;
-constexpr int kIdxHead = kBandBase + kBands + 1;
-constexpr int kFine = 256;
-constexpr int kFineWords = kFine * kFine / 16;
-
-template <typename T>
-struct alignas(16) Edge {
-  T ax, ay, bx, by;
-  T il2;            // 1 / |edge|^2 (0 for a degenerate edge)
-  uint32_t poly;    // polygon id
-};
-
+// the island map as the kernels see it: edge records, packed index and class grid in the format of
+// sit_map_format.h, built on the host by build_map_image (sit_map_build.h)
 template <typename T>
 struct Map {
   const Edge<T>* edge;      // [n_edge] (LDS copy in the step kernel)

@@ -18,7 +18,7 @@
 #ifndef SIT_EPISODES_H
 #define SIT_EPISODES_H
 
-#include "sit_impl.h"
+#include "sit_host.h"
 
 namespace {
 

@@ -1,15 +1,14 @@
 // sit_kernels.hip — C ABI of the ship-in-transit env step (include/sit.h) on MI355X (gfx950).
-// Kernels and host helpers: sit_impl.h.  float32 step kernels: sit_steps_f32.hip.
+// Kernels: sit_impl.h.  Handle, layouts, constants and launchers: sit_host.h.  The map image:
+// sit_map_build.h.  float32 step kernels: sit_steps_f32.hip.
 
-#include "sit_impl.h"
+#include "sit_host.h"
+#include "sit_map_build.h"
 #include "sit_actor.h"
 #include "sit_episodes.h"
 #include "sit_replay.h"
 
-namespace {
-
 #ifdef SIT_F32_TU
-}  // namespace
 int sit_launch_steps_f32(sit_handle* h, const void* io, void* stream);   // sit_steps_f32.hip
 int sit_launch_probe_f32(sit_handle* h, int n, const void* pts_ne, void* dist, uint8_t* inside, uint8_t* hull,
                          void* stream);
@@ -18,27 +17,59 @@ int sit_role_fallbacks_f32tu(unsigned long long* out, int reset);
 #ifdef SIT_DEBUG
 int sit_debug_flags_f32tu(uint32_t* out);
 #endif
+#endif
+
 namespace {
-int launch_steps_f32(sit_handle* h, const StepIO<float>& io, void* stream) {
-  return sit_launch_steps_f32(h, &io, stream);
+
+// The step and probe launches by real type (the probe's by a tag; its arrays are untyped).  float64
+// runs in this translation unit; float32 goes to the fast-math unit in the two-unit build and is
+// compiled here, strict, in single-unit (diagnostic) builds.  The generic code under with_real
+// calls steps / probe and stays oblivious to the split.
+int steps(sit_handle* h, const StepIO<double>& io, void* stream) {
+  return launch_steps<double>(h, io, (hipStream_t)stream);
 }
-int launch_probe_f32(sit_handle* h, int n, const void* pts, void* dist, uint8_t* inside, uint8_t* hull, void* stream) {
+int probe(sit_handle* h, double, int n, const void* pts, void* dist, uint8_t* inside, uint8_t* hull, void* stream) {
+  return launch_probe<double>(h, n, pts, dist, inside, hull, (hipStream_t)stream);
+}
+#ifdef SIT_F32_TU
+int steps(sit_handle* h, const StepIO<float>& io, void* stream) { return sit_launch_steps_f32(h, &io, stream); }
+int probe(sit_handle* h, float, int n, const void* pts, void* dist, uint8_t* inside, uint8_t* hull, void* stream) {
   return sit_launch_probe_f32(h, n, pts, dist, inside, hull, stream);
 }
 int launch_selftest_f32tu(int op, int n, const double* a, const double* b, double* out, void* stream) {
   return sit_launch_selftest_f32tu(op, n, a, b, out, stream);
 }
-#else   // single-TU build (diagnostic builds): float32 step kernels compiled here, strict fp
-int launch_steps_f32(sit_handle* h, const StepIO<float>& io, void* stream) {
+#else
+int steps(sit_handle* h, const StepIO<float>& io, void* stream) {
   return launch_steps<float>(h, io, (hipStream_t)stream);
 }
-int launch_probe_f32(sit_handle* h, int n, const void* pts, void* dist, uint8_t* inside, uint8_t* hull, void* stream) {
+int probe(sit_handle* h, float, int n, const void* pts, void* dist, uint8_t* inside, uint8_t* hull, void* stream) {
   return launch_probe<float>(h, n, pts, dist, inside, hull, (hipStream_t)stream);
 }
 int launch_selftest_f32tu(int op, int n, const double* a, const double* b, double* out, void* stream) {
   return launch_selftest(op, n, a, b, out, (hipStream_t)stream);
 }
 #endif
+
+// n doubles as the handle's reals (real_size 8: copied, 4: rounded to float)
+std::vector<unsigned char> to_real(const double* src, size_t n, size_t real_size) {
+  std::vector<unsigned char> out(n * real_size);
+  for (size_t i = 0; i < n; ++i) {
+    if (real_size == 8) reinterpret_cast<double*>(out.data())[i] = src[i];
+    else reinterpret_cast<float*>(out.data())[i] = (float)src[i];
+  }
+  return out;
+}
+
+// sit_step / sit_step_host: one step on explicit actions
+template <typename T>
+StepIO<T> single_step_io(const void* action_ne, const uint8_t* sac_update, const uint8_t* init, void* next_state,
+                         void* reward, uint8_t* done, uint32_t* status) {
+  StepIO<T> io{};
+  io.n_steps = 1; io.action_ne = (const T*)action_ne; io.sac_update = sac_update; io.init = init;
+  io.next_state = (T*)next_state; io.reward = (T*)reward; io.done = done; io.status = status;
+  return io;
+}
 
 }  // namespace
 
@@ -65,8 +96,7 @@ int sit_probe_map(sit_handle* h, int32_t n, const void* pts_ne, void* dist, uint
   if (!h->have_map) return fail(h, SIT_E_STATE, "sit_load_map has not been called");
   if (n < 0 || (n > 0 && !pts_ne)) return fail(h, SIT_E_INVALID, "need n >= 0 points");
   if (n == 0) return SIT_OK;
-  if (h->precision == SIT_F64) return launch_probe<double>(h, n, pts_ne, dist, inside, hull, (hipStream_t)stream);
-  return launch_probe_f32(h, n, pts_ne, dist, inside, hull, stream);
+  return with_real(h, [&](auto t) { return probe(h, t, n, pts_ne, dist, inside, hull, stream); });
 }
 
 int sit_selftest_f64(int32_t op, int32_t n, const double* a, const double* b, double* out, int32_t fast_tu,
@@ -85,14 +115,12 @@ int sit_policy_apply(sit_handle* h, int32_t capacity, const void* head, int32_t 
       !policy_ready || (!deterministic && !noise))
     return fail(h, SIT_E_INVALID, "policy_apply: bad arguments");
   const int blocks = (capacity + 255) / 256;
-  if (h->precision == SIT_F64)
-    hipLaunchKernelGGL(k_policy_apply<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, capacity,
-                       (const double*)head, head_stride, (const double*)noise, request_env, request_count,
-                       deterministic, (double*)policy_action, policy_ready, (unsigned long long*)served, h->n_env);
-  else
-    hipLaunchKernelGGL(k_policy_apply<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, capacity,
-                       (const float*)head, head_stride, (const float*)noise, request_env, request_count,
-                       deterministic, (float*)policy_action, policy_ready, (unsigned long long*)served, h->n_env);
+  with_real(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_policy_apply<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, capacity,
+                       (const T*)head, head_stride, (const T*)noise, request_env, request_count,
+                       deterministic, (T*)policy_action, policy_ready, (unsigned long long*)served, h->n_env);
+  });
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
 }
@@ -105,13 +133,11 @@ int sit_policy_actor(sit_handle* h, int32_t capacity, const float* weights, cons
   if (capacity <= 0 || !weights || !obs || !request_env || !request_count || !policy_action || !policy_ready ||
       (!deterministic && !noise))
     return fail(h, SIT_E_INVALID, "policy_actor: bad arguments");
-  int rc = h->precision == SIT_F64
-               ? launch_policy_actor<double>(h, capacity, weights, obs, noise, request_env, request_count,
-                                             deterministic, policy_action, policy_ready, served, clear_count,
-                                             (hipStream_t)stream)
-               : launch_policy_actor<float>(h, capacity, weights, obs, noise, request_env, request_count,
+  int rc = with_real(h, [&](auto t) {
+    return launch_policy_actor<decltype(t)>(h, capacity, weights, obs, noise, request_env, request_count,
                                             deterministic, policy_action, policy_ready, served, clear_count,
                                             (hipStream_t)stream);
+  });
   if (rc) return rc;
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
@@ -120,7 +146,8 @@ int sit_policy_actor(sit_handle* h, int32_t capacity, const float* weights, cons
 int sit_map_info(const sit_handle* h, int64_t* info, int32_t n) {
   if (!h || !info || n < 0) return SIT_E_INVALID;
   if (!h->have_map) return SIT_E_STATE;
-  const int64_t v[6] = {(int64_t)h->map_bytes, h->n_mixed, h->n_live, h->use_index, h->use_cells,
+  const MapMeta& m = h->meta;
+  const int64_t v[6] = {(int64_t)m.map_bytes, m.n_mixed, m.n_live, m.use_index, m.use_cells,
                         (int64_t)map_lds_bytes(h)};
   for (int i = 0; i < n && i < 6; ++i) info[i] = v[i];
   return SIT_OK;
@@ -257,35 +284,8 @@ int sit_create(const sit_params* p, int32_t n_env, int32_t wpt_capacity, int32_t
   if (const char* fs = getenv("SIT_TEST_FAKE_SIMDS")) h->fake_simds = 0x100 | (atoi(fs) & 0xFF);
   hipError_t e = setup_device(&h->device);
   if (e != hipSuccess) { fail(nullptr, SIT_E_HIP, "hipGetDevice: %s", hipGetErrorString(e)); delete h; return SIT_E_HIP; }
-  const size_t rs = real_size(h);
-  size_t off = 0;
-  for (int f = 0; f < kNumFields; ++f) {
-    int64_t cnt = kFields[f].extent == kShip ? 2LL * n_env
-                 : kFields[f].extent == kEnv ? (int64_t)n_env
-                 : kFields[f].extent == kObs ? (int64_t)SIT_OBS_DIM * n_env
-                 : kFields[f].extent == kLogRow ? (int64_t)SIT_LOG_KEYS * n_env : 2LL * wpt_capacity * n_env;
-    const size_t el = kFields[f].dtype == SIT_DT_REAL ? rs : 4;
-    h->off[f] = off;
-    h->count[f] = cnt;
-    off = align256(off + (size_t)cnt * el);
-  }
-  h->blob_bytes = off;
-  // scenario
-  size_t so = 0;
-  h->scen_init = so; so = align256(so + (size_t)2 * SIT_INIT_NF * n_env * rs);
-  h->scen_init_lo = so; so = align256(so + (size_t)2 * SIT_INIT_NF * n_env * rs);
-  h->scen_end_n = so; so = align256(so + (size_t)2 * n_env * rs);
-  h->scen_end_e = so; so = align256(so + (size_t)2 * n_env * rs);
-  h->scen_nw0 = so; so = align256(so + (size_t)2 * n_env * 4);
-  h->scen_ab_len = so; so = align256(so + (size_t)n_env * 8);
-  h->scen_ab_alpha = so; so = align256(so + (size_t)n_env * 8);
-  h->scen_initial = so; so = align256(so + (size_t)n_env * SIT_OBS_DIM * rs);
-  // policy-mode admission scratch (sit_actor.h): per 64-env group the age-bucket counts and the plan
-  const size_t n_groups = ((size_t)n_env + kAdmitGroup - 1) / kAdmitGroup;
-  h->scen_admit = so; so = align256(so + (n_groups * (kAgeBuckets + 2) + 16) * 4);
-  // in-kernel serving's fallback queue (logged policy launches): capacity n_env, zero ages
-  h->scen_serve = so; so = align256(so + (size_t)n_env * (3 * 4 + (SIT_OBS_DIM + 1) * rs) + 256);
-  h->scen_bytes = so;
+  layout_state(h);
+  layout_scen(h);
   if (setup_alloc(&h->blob, h->blob_bytes) != hipSuccess || setup_alloc(&h->scen, h->scen_bytes) != hipSuccess) {
     fail(nullptr, SIT_E_NOMEM, "hipMalloc of %zu + %zu bytes failed", h->blob_bytes, h->scen_bytes);
     sit_destroy(h);
@@ -322,259 +322,11 @@ int sit_load_map(sit_handle* h, int32_t n_poly, const int32_t* vert_offsets, con
     if (vert_offsets[p + 1] - vert_offsets[p] < 3) return fail(h, SIT_E_INVALID, "polygon %d has < 3 vertices", p);
   const int nv = vert_offsets[n_poly];
   if (nv > kMaxPolyVerts) return fail(h, SIT_E_INVALID, "at most %d vertices (got %d)", kMaxPolyVerts, nv);
-  const size_t rs = real_size(h);
-  std::vector<double> vx(nv), vy(nv), il2(nv), bbox(4 * n_poly);
-  std::vector<int32_t> nxt(nv), offs(vert_offsets, vert_offsets + n_poly + 1);
-  // PolygonObstacle.map_boundaries (obstacle.py:111-124): vertices are (east, north)
-  h->min_e = h->min_n = INFINITY;
-  h->max_e = h->max_n = -INFINITY;
-  for (int p = 0; p < n_poly; ++p) {
-    double bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
-    for (int i = offs[p]; i < offs[p + 1]; ++i) {
-      vx[i] = verts_en[2 * i];
-      vy[i] = verts_en[2 * i + 1];
-      nxt[i] = (i + 1 < offs[p + 1]) ? i + 1 : offs[p];
-      bx0 = std::min(bx0, vx[i]); bx1 = std::max(bx1, vx[i]);
-      by0 = std::min(by0, vy[i]); by1 = std::max(by1, vy[i]);
-    }
-    bbox[4 * p + 0] = bx0; bbox[4 * p + 1] = bx1; bbox[4 * p + 2] = by0; bbox[4 * p + 3] = by1;
-    h->min_e = std::min(h->min_e, bx0); h->max_e = std::max(h->max_e, bx1);
-    h->min_n = std::min(h->min_n, by0); h->max_n = std::max(h->max_n, by1);
-  }
-  std::vector<double> bxv(nv), byv(nv);
-  for (int i = 0; i < nv; ++i) {
-    bxv[i] = vx[nxt[i]];
-    byv[i] = vy[nxt[i]];
-    const double ex = bxv[i] - vx[i], ey = byv[i] - vy[i];
-    const double l2 = ex * ex + ey * ey;
-    il2[i] = l2 > 0 ? 1.0 / l2 : 0.0;
-  }
-  // ---- spatial index (see sit_device.h): conservative nearest-edge candidates per grid cell,
-  //      edges per horizontal band.  Exact by construction; 1 m slack covers float rounding.
-  std::vector<int> poly_of(nv);
-  for (int p = 0; p < n_poly; ++p)
-    for (int i = offs[p]; i < offs[p + 1]; ++i) poly_of[i] = p;
-  const double ext_x = h->max_e - h->min_e, ext_y = h->max_n - h->min_n;
-  const double mg = 0.1 * std::max(ext_x, ext_y) + 500.0;
-  const double gx0 = h->min_e - mg, gy0 = h->min_n - mg;
-  const double sx = (ext_x + 2 * mg) / kGrid, sy = (ext_y + 2 * mg) / kGrid;
-  const double hd = 0.5 * std::sqrt(sx * sx + sy * sy) + 1.0;
-  auto seg_dist = [&](double px, double py, int i) {
-    const double ex = bxv[i] - vx[i], ey = byv[i] - vy[i], l2 = ex * ex + ey * ey;
-    double t = l2 > 0 ? ((px - vx[i]) * ex + (py - vy[i]) * ey) / l2 : 0.0;
-    t = std::min(1.0, std::max(0.0, t));
-    return std::hypot(px - (vx[i] + t * ex), py - (vy[i] + t * ey));
-  };
-  // packed u16 index: [grid records (u32 per cell)][band starts (NB+1)][band entries][grid groups]
-  std::vector<uint16_t> gentries, bentries;
-  std::vector<uint32_t> gstart(kGrid * kGrid + 1), bstart(kBands + 1);
-  std::vector<double> dcell(nv);
-  std::vector<int> cand;
-  constexpr int kSamples = 64;   // per cell side for the candidate refinement
-  for (int j = 0; j < kGrid; ++j)
-    for (int i = 0; i < kGrid; ++i) {
-      const double cx = gx0 + (i + 0.5) * sx, cy = gy0 + (j + 0.5) * sy;
-      double D = INFINITY;
-      for (int e = 0; e < nv; ++e) { dcell[e] = seg_dist(cx, cy, e); D = std::min(D, dcell[e] + hd); }
-      gstart[j * kGrid + i] = (uint32_t)gentries.size();
-      const size_t first = gentries.size();
-      // conservative prefilter, then the Lipschitz refinement: for every point p of the cell
-      // grown by 1 m, some sample s lies within r; the nearest edge e* of p has
-      // d_e*(s) <= d*(p) + r and min_f d_f(s) >= d*(p) - r, so e* is kept by
-      // d_e(s) <= min_f d_f(s) + 2r + 1 m at some sample.  A dropped edge is >= 1 m farther than
-      // the nearest at every point of the grown cell, so float rounding cannot make it the
-      // minimum: the minimum over the list equals the full scan's.
-      cand.clear();
-      for (int e = 0; e < nv; ++e)
-        if (dcell[e] - hd <= D + 1.0) cand.push_back(e);
-      if (cand.size() > 1) {
-        const double x0 = gx0 + i * sx - 1.0, y0 = gy0 + j * sy - 1.0;
-        const double dx = (sx + 2.0) / kSamples, dy = (sy + 2.0) / kSamples;
-        const double r2 = std::sqrt(dx * dx + dy * dy) + 1.0;   // 2r + 1 m
-        std::vector<char> keep(cand.size(), 0);
-        std::vector<double> dd(cand.size());
-        for (int v = 0; v < kSamples; ++v)
-          for (int u = 0; u < kSamples; ++u) {
-            const double px = x0 + (u + 0.5) * dx, py = y0 + (v + 0.5) * dy;
-            double m = INFINITY;
-            for (size_t q = 0; q < cand.size(); ++q) { dd[q] = seg_dist(px, py, cand[q]); m = std::min(m, dd[q]); }
-            for (size_t q = 0; q < cand.size(); ++q) keep[q] |= dd[q] <= m + r2;
-          }
-        size_t w = 0;
-        for (size_t q = 0; q < cand.size(); ++q)
-          if (keep[q]) cand[w++] = cand[q];
-        cand.resize(w);
-      }
-      // groups of 5 u8 ids in 8 bytes (padded with the list's first id): every list of the
-      // reference map fits one group (lists of 5 near some vertices would need two groups of 4)
-      while (cand.size() % 5) cand.push_back(cand[0]);
-      for (size_t q = 0; q < cand.size(); q += 5) {
-        gentries.push_back((uint16_t)(cand[q] | (cand[q + 1] << 8)));
-        gentries.push_back((uint16_t)(cand[q + 2] | (cand[q + 3] << 8)));
-        gentries.push_back((uint16_t)cand[q + 4]);
-        gentries.push_back(0);
-      }
-      (void)first;
-    }
-  gstart[kGrid * kGrid] = (uint32_t)gentries.size();
-  const double by0 = h->min_n - 1.0, bh = (ext_y + 2.0) / kBands;
-  for (int b = 0; b < kBands; ++b) {
-    bstart[b] = (uint32_t)bentries.size();
-    const double lo = by0 + b * bh - 1.0, hi = by0 + (b + 1) * bh + 1.0;
-    for (int e = 0; e < nv; ++e)
-      if (std::min(vy[e], byv[e]) <= hi && std::max(vy[e], byv[e]) >= lo) bentries.push_back((uint16_t)e);
-  }
-  bstart[kBands] = (uint32_t)bentries.size();
-  // point-in-polygon by crossing number for class-grid cell centres (>= 1 m off every edge)
-  auto inside_center = [&](double px, double py) {
-    bool in = false;
-    for (int p = 0; p < n_poly; ++p) {
-      int cross = 0;
-      for (int i = offs[p]; i < offs[p + 1]; ++i) {
-        const double x1 = vx[i], y1 = vy[i], x2 = bxv[i], y2 = byv[i];
-        if ((y1 > py) != (y2 > py)) {
-          const double xi = x1 + (py - y1) * (x2 - x1) / (y2 - y1);
-          if (xi > px) ++cross;
-        }
-      }
-      in |= (cross & 1) != 0;
-    }
-    return in;
-  };
-  // fine 2-bit classes over the map extent + 100 m
-  const double fx0 = h->min_e - 100.0, fy0 = h->min_n - 100.0;
-  const double fsx = (ext_x + 200.0) / kFine, fsy = (ext_y + 200.0) / kFine;
-  const double fhd = 0.5 * std::sqrt(fsx * fsx + fsy * fsy) + 1.0;
-  std::vector<uint32_t> fine(kFineWords, 0);
-  for (int j = 0; j < kFine; ++j)
-    for (int i = 0; i < kFine; ++i) {
-      const double cx = fx0 + (i + 0.5) * fsx, cy = fy0 + (j + 0.5) * fsy;
-      double dmin = INFINITY;
-      for (int e = 0; e < nv && dmin > fhd + 1.0; ++e) dmin = std::min(dmin, seg_dist(cx, cy, e));
-      const uint32_t k = dmin > fhd + 1.0 ? (inside_center(cx, cy) ? 1u : 0u) : 2u;
-      const int cell = j * kFine + i;
-      fine[cell >> 4] |= k << ((cell & 15) * 2);
-    }
-  h->fx0 = fx0; h->fy0 = fy0; h->finvx = 1.0 / fsx; h->finvy = 1.0 / fsy;
-  // point-in-polygon records of the mixed cells (see Map in sit_device.h).  An edge's GEOS
-  // crossing contribution is the same for every point of cell [x0,x1]x[y0,y1] when (1 m
-  // margin, far above float rounding of coordinates <= 1e5 m): it lies wholly left of the cell
-  // (early return), its y-range misses the cell's rows, or it spans the rows strictly and,
-  // within them, lies wholly right or wholly left of the cell (then it straddles every row and
-  // its orientation against every point is that against the centre).  All other edges are live.
-  std::vector<uint16_t> frank(kFineWords, 0);
-  std::vector<uint32_t> crec;
-  std::vector<uint8_t> clive;
-  {
-    int rank = 0;
-    for (int w = 0; w < kFineWords; ++w) {
-      frank[w] = (uint16_t)std::min(rank, 65535);
-      rank += __builtin_popcount((fine[w] >> 1) & 0x55555555u);
-    }
-    for (int cell = 0; cell < kFine * kFine; ++cell) {
-      if (((fine[cell >> 4] >> ((cell & 15) * 2)) & 3) != 2) continue;
-      const int i = cell % kFine, j = cell / kFine;
-      const double x0 = fx0 + i * fsx, x1 = fx0 + (i + 1) * fsx, y0 = fy0 + j * fsy, y1 = fy0 + (j + 1) * fsy;
-      const double cx = 0.5 * (x0 + x1), cy = 0.5 * (y0 + y1), mgn = 1.0;
-      uint32_t par = 0;
-      const size_t first = clive.size();
-      for (int e = 0; e < nv; ++e) {
-        const double p1x = vx[e], p1y = vy[e], p2x = bxv[e], p2y = byv[e];
-        const double xmax = std::max(p1x, p2x), ymin = std::min(p1y, p2y), ymax = std::max(p1y, p2y);
-        if (xmax < x0 - mgn) continue;                          // left of every point: no count
-        if (ymax < y0 - mgn || ymin > y1 + mgn) continue;       // never straddles a cell row
-        if (ymin < y0 - mgn && ymax > y1 + mgn) {
-          const double ta = (y0 - mgn - p1y) / (p2y - p1y), tb = (y1 + mgn - p1y) / (p2y - p1y);
-          const double xa = p1x + ta * (p2x - p1x), xb = p1x + tb * (p2x - p1x);
-          const bool right = std::min(xa, xb) > x1 + mgn && xmax > x1 + mgn;
-          const bool left = std::max(xa, xb) < x0 - mgn && xmax > x1 + mgn;
-          if (right || left) {
-            const double det = (p1x - cx) * (p2y - cy) - (p1y - cy) * (p2x - cx);
-            const int o = (det > 0) - (det < 0);
-            const int oo = (p2y < p1y) ? -o : o;
-            if (oo > 0) par ^= 1u << poly_of[e];
-            continue;
-          }
-        }
-        clive.push_back((uint8_t)e);
-      }
-      const size_t cnt = clive.size() - first;
-      crec.push_back(par);
-      crec.push_back((uint32_t)first | ((uint32_t)cnt << 16));
-    }
-  }
-  const bool cells_ok = crec.size() / 2 <= 65535 && clive.size() <= 65535;
-  // each cell's first group goes into its record; the further groups (lists of > 5) follow the
-  // band entries
-  std::vector<uint16_t> grest;
-  std::vector<uint32_t> rstart(kGrid * kGrid);
-  for (int c = 0; c < kGrid * kGrid; ++c) {
-    rstart[c] = (uint32_t)grest.size();
-    grest.insert(grest.end(), gentries.begin() + gstart[c] + 4, gentries.begin() + gstart[c + 1]);
-  }
-  const size_t head = (size_t)kIdxHead;
-  const size_t gbase = (head + bentries.size() + 3) & ~size_t(3);   // 8-byte aligned groups
-  const size_t n_idx = gbase + grest.size();
-  h->use_index = (n_idx < 65535 && n_idx * 2 <= 48 * 1024) ? 1 : 0;
-  h->gx0 = gx0; h->gy0 = gy0; h->ginvx = 1.0 / sx; h->ginvy = 1.0 / sy;
-  h->by0 = by0; h->binv = 1.0 / bh;
-  std::vector<uint16_t> idx(h->use_index ? n_idx : 4, 0);
-  h->n_idx = (int64_t)idx.size();
-  if (h->use_index) {
-    for (int c = 0; c < kGrid * kGrid; ++c) {
-      const uint16_t* f = gentries.data() + gstart[c];
-      const uint32_t more = (gstart[c + 1] - gstart[c]) / 4 - 1;    // < 52: ids are u8, 5 per group
-      const uint32_t y = (f[2] & 0xffu) | (more << 8) | ((uint32_t)((gbase + rstart[c]) / 4) << 16);
-      idx[4 * c] = f[0];                       // ids 0, 1
-      idx[4 * c + 1] = f[1];                   // ids 2, 3
-      idx[4 * c + 2] = (uint16_t)(y & 0xffffu);
-      idx[4 * c + 3] = (uint16_t)(y >> 16);
-    }
-    for (int b = 0; b <= kBands; ++b) idx[kBandBase + b] = (uint16_t)(head + bstart[b]);
-    std::copy(bentries.begin(), bentries.end(), idx.begin() + head);
-    std::copy(grest.begin(), grest.end(), idx.begin() + gbase);
-  }
-  // blob: [Edge<T>[nv]][u16 index][u32 classes] (staged into LDS) [ring offsets][bboxes] (fallback, global)
-  const size_t esz = rs == 8 ? sizeof(Edge<double>) : sizeof(Edge<float>);
-  size_t o = align256(nv * esz);
-  h->map_idx = o; o = align256(o + idx.size() * 2);
-  h->map_fine = o; o = align256(o + fine.size() * 4);
-  h->use_cells = cells_ok ? 1 : 0;
-  h->n_mixed = (int64_t)crec.size() / 2;
-  h->n_live = (int64_t)clive.size();
-  h->map_frank = o; o += (cells_ok ? frank.size() * 2 : 0); o = (o + 7) & ~size_t(7);
-  h->map_crec = o; o += (cells_ok ? crec.size() * 4 : 0);
-  h->map_clive = o; o = align256(o + (cells_ok ? clive.size() : 0));
-  h->map_bytes = o;
-  h->map_off = o; o = align256(o + (n_poly + 1) * 4);
-  h->map_bbox = o; o = align256(o + 4 * n_poly * rs);
-  std::vector<unsigned char> host(o, 0);
-  for (int e = 0; e < nv; ++e) {
-    if (rs == 8) {
-      Edge<double> g{vx[e], vy[e], bxv[e], byv[e], il2[e], (uint32_t)poly_of[e]};
-      std::memcpy(host.data() + e * esz, &g, sizeof(g));
-    } else {
-      Edge<float> g{(float)vx[e], (float)vy[e], (float)bxv[e], (float)byv[e], (float)il2[e], (uint32_t)poly_of[e]};
-      std::memcpy(host.data() + e * esz, &g, sizeof(g));
-    }
-  }
-  std::memcpy(host.data() + h->map_idx, idx.data(), idx.size() * 2);
-  std::memcpy(host.data() + h->map_fine, fine.data(), fine.size() * 4);
-  if (cells_ok) {
-    std::memcpy(host.data() + h->map_frank, frank.data(), frank.size() * 2);
-    std::memcpy(host.data() + h->map_crec, crec.data(), crec.size() * 4);
-    if (!clive.empty()) std::memcpy(host.data() + h->map_clive, clive.data(), clive.size());
-  }
-  std::memcpy(host.data() + h->map_off, offs.data(), (n_poly + 1) * 4);
-  for (size_t i = 0; i < bbox.size(); ++i) {
-    if (rs == 8) reinterpret_cast<double*>(host.data() + h->map_bbox)[i] = bbox[i];
-    else reinterpret_cast<float*>(host.data() + h->map_bbox)[i] = (float)bbox[i];
-  }
+  const MapImage img = build_map_image(n_poly, vert_offsets, verts_en, real_size(h));
   if (h->map) { (void)setup_free(h->map); h->map = nullptr; }
-  HIP_TRY(h, setup_alloc(&h->map, o));
-  HIP_TRY(h, setup_upload(h->map, host.data(), o));
-  h->n_poly = n_poly;
-  h->n_vert = nv;
+  HIP_TRY(h, setup_alloc(&h->map, img.bytes.size()));
+  HIP_TRY(h, setup_upload(h->map, img.bytes.data(), img.bytes.size()));
+  h->meta = img.meta;
   h->have_map = true;
   // the cached IW tests describe the previous map
   HIP_TRY(h, setup_zero(h->blob + h->off[F_IWK_FLAGS], (size_t)h->n_env * 4));
@@ -607,17 +359,9 @@ int sit_load_routes(sit_handle* h, const double* wpt_ne, const int32_t* n_wpt) {
       }
     }
   }
-  auto conv = [&](const double* src, size_t cnt) {
-    std::vector<unsigned char> out(cnt * rs);
-    for (size_t i = 0; i < cnt; ++i) {
-      if (rs == 8) reinterpret_cast<double*>(out.data())[i] = src[i];
-      else reinterpret_cast<float*>(out.data())[i] = (float)src[i];
-    }
-    return out;
-  };
   const size_t tcnt = (size_t)2 * cap * n;
-  auto tn = conv(tab.data(), tcnt), te = conv(tab.data() + tcnt, tcnt);
-  auto en = conv(end.data(), (size_t)2 * n), ee = conv(end.data() + (size_t)2 * n, (size_t)2 * n);
+  auto tn = to_real(tab.data(), tcnt, rs), te = to_real(tab.data() + tcnt, tcnt, rs);
+  auto en = to_real(end.data(), (size_t)2 * n, rs), ee = to_real(end.data() + (size_t)2 * n, (size_t)2 * n, rs);
   HIP_TRY(h, setup_upload(h->blob + h->off[F_WN], tn.data(), tn.size()));
   HIP_TRY(h, setup_upload(h->blob + h->off[F_WE], te.data(), te.size()));
   HIP_TRY(h, setup_upload(h->scen + h->scen_end_n, en.data(), en.size()));
@@ -647,15 +391,7 @@ int sit_load_initial(sit_handle* h, const double* init) {
     o[0] = (float)a[SIT_INIT_NORTH]; o[1] = (float)a[SIT_INIT_EAST]; o[2] = (float)a[SIT_INIT_YAW];
     o[6] = (float)b[SIT_INIT_NORTH]; o[7] = (float)b[SIT_INIT_EAST]; o[8] = (float)b[SIT_INIT_YAW];
   }
-  auto conv = [&](const std::vector<double>& src) {
-    std::vector<unsigned char> out(src.size() * rs);
-    for (size_t i = 0; i < src.size(); ++i) {
-      if (rs == 8) reinterpret_cast<double*>(out.data())[i] = src[i];
-      else reinterpret_cast<float*>(out.data())[i] = (float)src[i];
-    }
-    return out;
-  };
-  auto a = conv(sc), b = conv(ist);
+  auto a = to_real(sc.data(), sc.size(), rs), b = to_real(ist.data(), ist.size(), rs);
   HIP_TRY(h, setup_upload(h->scen + h->scen_init, a.data(), a.size()));
   if (rs == 4) {   // float32: the low parts of the initial values (double-float starts, comp_add)
     std::vector<float> lo(sc.size());
@@ -671,10 +407,10 @@ int sit_restart(sit_handle* h, void* stream) {
   int rc = ready(h);
   if (rc) return rc;
   const int blocks = (h->n_env + 255) / 256;
-  if (h->precision == SIT_F64)
-    hipLaunchKernelGGL(k_restart<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<double>(h));
-  else
-    hipLaunchKernelGGL(k_restart<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<float>(h));
+  with_real(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_restart<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<T>(h));
+  });
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
 }
@@ -683,12 +419,11 @@ int sit_reset(sit_handle* h, const uint8_t* env_mask, void* initial_state, void*
   int rc = ready(h);
   if (rc) return rc;
   const int blocks = (h->n_env + 255) / 256;
-  if (h->precision == SIT_F64)
-    hipLaunchKernelGGL(k_reset<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<double>(h),
-                       env_mask, (double*)initial_state);
-  else
-    hipLaunchKernelGGL(k_reset<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<float>(h),
-                       env_mask, (float*)initial_state);
+  with_real(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_reset<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<T>(h), env_mask,
+                       (T*)initial_state);
+  });
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
 }
@@ -697,18 +432,17 @@ int sit_init_step(sit_handle* h, const uint8_t* env_mask, void* stream) {
   int rc = ready(h);
   if (rc) return rc;
   const int blocks = (2 * h->n_env + 255) / 256;
-  if (h->precision == SIT_F64)
-    hipLaunchKernelGGL(k_init_step<double>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<double>(h), env_mask);
-  else
-    hipLaunchKernelGGL(k_init_step<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<float>(h), env_mask);
+  with_real(h, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_init_step<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, make_args<T>(h), env_mask);
+  });
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
 }
 
 // next_state and action_out rows are written with paired stores (store2)
 static bool pair_aligned(const sit_handle* h, const void* p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  return (a % (2 * (h->precision == SIT_F64 ? sizeof(double) : sizeof(float)))) == 0;
+  return reinterpret_cast<uintptr_t>(p) % (2 * real_size(h)) == 0;
 }
 
 int sit_step(sit_handle* h, const void* action_ne, const uint8_t* sac_update, const uint8_t* init,
@@ -719,18 +453,11 @@ int sit_step(sit_handle* h, const void* action_ne, const uint8_t* sac_update, co
   if (!action_ne || !sac_update || !init) return fail(h, SIT_E_INVALID, "action_ne, sac_update and init are required");
   if (!next_state && !reward) return fail(h, SIT_E_INVALID, "need next_state or reward output");
   if (!pair_aligned(h, next_state)) return fail(h, SIT_E_INVALID, "next_state must be aligned to 2 reals");
-  if (h->precision == SIT_F64) {
-    StepIO<double> io{};
-    io.n_steps = 1; io.action_ne = (const double*)action_ne; io.sac_update = sac_update; io.init = init;
-    io.next_state = (double*)next_state; io.reward = (double*)reward; io.done = done; io.status = status;
+  return with_real(h, [&](auto t) {
+    auto io = single_step_io<decltype(t)>(action_ne, sac_update, init, next_state, reward, done, status);
     io.done_count = done_count;
-    return launch_steps<double>(h, io, (hipStream_t)stream);
-  }
-  StepIO<float> io{};
-  io.n_steps = 1; io.action_ne = (const float*)action_ne; io.sac_update = sac_update; io.init = init;
-  io.next_state = (float*)next_state; io.reward = (float*)reward; io.done = done; io.status = status;
-  io.done_count = done_count;
-  return launch_steps_f32(h, io, stream);
+    return steps(h, io, stream);
+  });
 }
 
 // sit_step_host's staging: pinned, coherent host memory mapped for the device (the step kernel reads
@@ -784,19 +511,12 @@ int sit_step_host(sit_handle* h, const void* action_ne, const uint8_t* sac_updat
   std::memcpy(h->stage + L.init, init, n);
   unsigned char* d = h->stage_dev;
   hipStream_t s = (hipStream_t)stream;
-  if (h->precision == SIT_F64) {
-    StepIO<double> io{};
-    io.n_steps = 1; io.action_ne = (const double*)(d + L.act); io.sac_update = d + L.sac; io.init = d + L.init;
-    io.next_state = (double*)(d + L.ns); io.reward = (double*)(d + L.rw); io.done = d + L.dn;
-    io.status = (uint32_t*)(d + L.st); io.log = log ? (double*)(d + L.log) : nullptr;
-    rc = launch_steps<double>(h, io, s);
-  } else {
-    StepIO<float> io{};
-    io.n_steps = 1; io.action_ne = (const float*)(d + L.act); io.sac_update = d + L.sac; io.init = d + L.init;
-    io.next_state = (float*)(d + L.ns); io.reward = (float*)(d + L.rw); io.done = d + L.dn;
-    io.status = (uint32_t*)(d + L.st); io.log = log ? (float*)(d + L.log) : nullptr;
-    rc = launch_steps_f32(h, io, stream);
-  }
+  rc = with_real(h, [&](auto t) {
+    using T = decltype(t);
+    auto io = single_step_io<T>(d + L.act, d + L.sac, d + L.init, d + L.ns, d + L.rw, d + L.dn, (uint32_t*)(d + L.st));
+    io.log = log ? (T*)(d + L.log) : nullptr;
+    return steps(h, io, stream);
+  });
   if (rc) return rc;
   if (state) HIP_TRY(h, hipMemcpyAsync(h->stage + L.blob, h->blob, h->blob_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
@@ -836,8 +556,8 @@ int sit_rollout(sit_handle* h, const sit_rollout_args* ra, void* stream) {
     return fail(h, SIT_E_INVALID, "policy mode needs policy_ready, request_env, request_noise, "
                                   "request_obs, request_count, request_age and a positive request_capacity "
                                   "(or actor_weights: in-kernel serving)");
-  auto fill = [&](auto* io, auto* tag) {
-    using R = std::remove_pointer_t<decltype(tag)>;
+  auto fill = [&](auto* io) {
+    using R = std::remove_pointer_t<decltype(io->next_state)>;
     io->n_steps = ra->n_steps; io->auto_reset = ra->auto_reset; io->seed = ra->seed;
     io->env_id_offset = ra->env_id_offset;
     io->action_ne = (const R*)ra->action_ne; io->sac_update = ra->sac_update; io->init = ra->init;
@@ -858,9 +578,8 @@ int sit_rollout(sit_handle* h, const sit_rollout_args* ra, void* stream) {
   // policy mode: the step kernel, then the deterministic admission of the waiting envs into the
   // request queue (k_policy_admit, sit_actor.h) on the same stream — or, serving in the kernel, nothing;
   // a serving launch that takes the one-wave kernel (logged) is served through the library's own queue
-  auto run = [&](auto* io, auto launch) -> int {
-    using R = std::remove_pointer_t<decltype(io->next_state)>;
-    sit_rollout_args q = *ra;
+  auto run = [&](auto* io) -> int {
+    using R = std::remove_pointer_t<decltype(io->next_state)>;    sit_rollout_args q = *ra;
     if (serve && sync_launch_lds<R>(h, *io, nullptr, nullptr) == 0) {
       const ServeQueue sq = serve_queue(h);
       io->actor_w = nullptr;
@@ -869,9 +588,9 @@ int sit_rollout(sit_handle* h, const sit_rollout_args* ra, void* stream) {
       q.request_capacity = h->n_env; q.request_env = sq.env; q.request_obs = sq.obs; q.request_noise = sq.noise;
       q.request_count = sq.count; q.request_age = sq.age;
     } else if (serve) {
-      return launch(*io);
+      return steps(h, *io, stream);
     }
-    int r = launch(*io);
+    int r = steps(h, *io, stream);
     if (r == SIT_OK && ra->policy_action) r = launch_policy_admit<R>(h, &q, (hipStream_t)stream);
     if (r == SIT_OK && serve)
       r = launch_policy_actor<R>(h, h->n_env, ra->actor_weights, q.request_obs, q.request_noise, q.request_env,
@@ -879,15 +598,11 @@ int sit_rollout(sit_handle* h, const sit_rollout_args* ra, void* stream) {
                                  ra->policy_ready, ra->actor_served, nullptr, (hipStream_t)stream);
     return r;
   };
-  if (h->precision == SIT_F64) {
-    StepIO<double> io{};
-    fill(&io, (double*)nullptr);
-    rc = run(&io, [&](const StepIO<double>& x) { return launch_steps<double>(h, x, (hipStream_t)stream); });
-  } else {
-    StepIO<float> io{};
-    fill(&io, (float*)nullptr);
-    rc = run(&io, [&](const StepIO<float>& x) { return launch_steps_f32(h, x, stream); });
-  }
+  rc = with_real(h, [&](auto t) {
+    StepIO<decltype(t)> io{};
+    fill(&io);
+    return run(&io);
+  });
   if (rc) return rc;
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
@@ -952,8 +667,7 @@ int sit_episodes_update(sit_handle* h, const sit_episodes_args* a, void* stream)
     int rc = sit_episodes_reset(h, stream);
     if (rc) return rc;
   }
-  return h->precision == SIT_F64 ? episodes_launch_update<double>(h, a, (hipStream_t)stream)
-                                 : episodes_launch_update<float>(h, a, (hipStream_t)stream);
+  return with_real(h, [&](auto t) { return episodes_launch_update<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
 int sit_episodes_bytes(const sit_handle* h, size_t* bytes) {
@@ -1004,8 +718,7 @@ int sit_replay_push(sit_handle* h, const sit_replay_push_args* a, void* stream) 
   const size_t quad = 4 * real_size(h);   // records are copied in 16-byte pieces
   if ((uintptr_t)a->ring % quad) return fail(h, SIT_E_INVALID, "replay: ring must be aligned to 4 reals (%zu bytes)", quad);
   if ((uintptr_t)a->src % quad) return fail(h, SIT_E_INVALID, "replay: src must be aligned to 4 reals (%zu bytes)", quad);
-  return h->precision == SIT_F64 ? replay_launch_push<double>(h, a, (hipStream_t)stream)
-                                 : replay_launch_push<float>(h, a, (hipStream_t)stream);
+  return with_real(h, [&](auto t) { return replay_launch_push<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
 int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream) {
@@ -1022,8 +735,7 @@ int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stre
     return fail(h, SIT_E_INVALID, "replay: every output (state, action, reward, next_state, mask, env, index) is required");
   const size_t quad = 4 * real_size(h);
   if ((uintptr_t)a->ring % quad) return fail(h, SIT_E_INVALID, "replay: ring must be aligned to 4 reals (%zu bytes)", quad);
-  return h->precision == SIT_F64 ? replay_launch_sample<double>(h, a, (hipStream_t)stream)
-                                 : replay_launch_sample<float>(h, a, (hipStream_t)stream);
+  return with_real(h, [&](auto t) { return replay_launch_sample<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

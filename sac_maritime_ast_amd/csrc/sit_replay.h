@@ -23,7 +23,7 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "sit_impl.h"
+#include "sit_host.h"
 
 namespace {
 

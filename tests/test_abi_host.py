@@ -1,5 +1,6 @@
 """CPU checks of the C-ABI library and the host-side package (no compute calls: no GPU here)."""
 import ctypes
+import json
 import os
 import re
 from types import SimpleNamespace
@@ -159,6 +160,10 @@ def test_setup_calls_host_logic(precision):
         info = np.zeros(6, dtype=np.int64)
         assert lib.sit_map_info(h, vp(info), 6) == 0
         assert info[0] > 0 and info[1] > 1000 and info[2] > 1000 and info[5] >= info[0]
+        # the scenario's map as recorded for tests/test_map_build_host.py
+        with open(os.path.join(ROOT, "tests", "golden", "map_images.json")) as f:
+            g = json.load(f)["scenario"][str(precision // 8)]
+        assert info.tolist() == [g[k] for k in ("map_bytes", "n_mixed", "n_live", "use_index", "use_cells", "lds_bytes")]
         routes = np.ascontiguousarray(sc.routes, dtype=np.float64)
         n_wpt = np.ascontiguousarray(sc.n_wpt, dtype=np.int32)
         assert lib.sit_load_routes(h, vp(routes), vp(n_wpt)) == 0, lib.sit_last_error(h)

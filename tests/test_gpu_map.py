@@ -1,7 +1,7 @@
 """GPU parity of the island-map predicates (sit_probe_map) against the oracle's GEOS restatement.
 
 The step kernel decides terrain hits and the boundary-distance reward term through a spatial
-index (nearest-edge grid, class grid, per-cell crossing records; sit_device.h).  The index must
+index (nearest-edge grid, class grid, per-cell crossing records; sit_map_format.h).  The index must
 reproduce the full scans of the reference's predicates exactly:
   * Polygon.contains               obstacle.py:126-129   (GEOS RayCrossingCounter)
   * exterior.distance              obstacle.py:138-141   (GEOS Distance::pointToSegment)
