@@ -579,6 +579,61 @@ int sit_replay_reserve(sit_handle* h, int32_t max_src_capacity, void* stream);
 int sit_replay_push(sit_handle* h, const sit_replay_push_args* a, void* stream);
 int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream);
 
+/* ---- SAC learner: the no-gradient half of an update ----------------------------------
+ * agent.update_parameters (test_beds/main_ast.py:350-362; twin Q networks of hidden size 256,
+ * main_ast.py:41-90) needs, per minibatch and without gradients, the actor at next_state with its
+ * log-probability, both target critics at (next_state, a'), the TD target, and afterwards the Polyak
+ * update of the targets.  Two calls, one kernel each, on the caller's stream; they validate their
+ * arguments (SIT_E_INVALID for a null required pointer, batch <= 0 or n <= 0, or a weight block that is
+ * not 16-byte aligned: nothing is launched), allocate nothing and never synchronise.
+ *
+ * Critic block: SIT_CRITIC_WEIGHTS float32 per critic, 11 -> 256 -> ReLU -> 256 -> ReLU -> 1 on
+ * concat(next_state, a'):  W1 [256][11] (torch Linear layout), b1 [256], W2 transposed [256 in][256 out],
+ * b2 [256], W3 [256], b3 [1], then zero padding to a multiple of 4 floats.  critic_weights holds two such
+ * blocks, Q1's then Q2's.  The actor block is sit_policy_actor's (SIT_ACTOR_WEIGHTS).
+ *
+ * sit_sac_target, for each row b < batch, networks and logp in float32:
+ *   (mu, ls) = actor(next_state[b]);  ls = clip(ls, -20, 2)
+ *   x = fma(exp(ls), eps, mu);  a' = tanh(x)
+ *   logp = -0.5 eps^2 - ls - 0.5 log(2 pi) - log(1 - tanh(x)^2 + 1e-6)
+ *   q_i = Q_i(concat(next_state[b], a')), i = 1, 2
+ *   y[b] = reward_scale * reward[b] + mask[b] * gamma * (min(q1, q2) - alpha * logp)   in the handle's real
+ * 1 - tanh(x)^2 is formed from x as 4 (em + 1) / (em + 2)^2, em = expm1(2 |x|), never as 1 - a' a'.
+ * eps is noise[b] when noise is given; otherwise a standard normal drawn per row from Philox4x32-10(key =
+ * (seed lo, seed hi), ctr = (b, 0x5441, update lo, update hi)) by the Box-Muller step of the policy's
+ * event noise: u1 = (2^26 (c0 >> 5) + (c1 >> 6) + 1) / 2^53, u2 = (2^26 (c2 >> 5) + (c3 >> 6)) / 2^53,
+ * eps = sqrt(-2 log u1) cos(2 pi u2), in float64, then rounded to float32.  alpha is read on the device.
+ * Deterministic; rows [0, batch) do not depend on batch.
+ *
+ * sit_sac_polyak: target[i] = fma(tau, online[i] - target[i], target[i]) in float32 for i < n, over any
+ * packed block (both critics at once: n = 2 SIT_CRITIC_WEIGHTS). */
+#define SIT_CRITIC_INPUT (SIT_OBS_DIM + 1)
+#define SIT_CRITIC_WEIGHTS \
+  ((SIT_ACTOR_HIDDEN * SIT_CRITIC_INPUT + SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN * SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN + \
+    SIT_ACTOR_HIDDEN + 1 + 3) / 4 * 4)
+typedef struct sit_sac_target_args {
+  int32_t batch;               /* rows B, > 0 */
+  uint64_t seed;               /* key of the noise draw (noise == NULL) */
+  uint64_t update;             /* counter words 2, 3 of the noise draw */
+  double gamma;
+  double reward_scale;
+  const float* actor_weights;  /* float[SIT_ACTOR_WEIGHTS], 16-byte aligned */
+  const float* critic_weights; /* float[2][SIT_CRITIC_WEIGHTS] (the target critics), 16-byte aligned */
+  const float* alpha;          /* float[1], device */
+  const void* next_state;      /* real[B][10] */
+  const void* reward;          /* real[B] */
+  const void* mask;            /* real[B] */
+  void* y;                     /* real[B] */
+  const void* noise;           /* real[B] or NULL (drawn on the device) */
+  void* next_action;           /* real[B] or NULL: a' */
+  void* next_logp;             /* real[B] or NULL */
+  void* q1;                    /* real[B] or NULL */
+  void* q2;                    /* real[B] or NULL */
+} sit_sac_target_args;
+size_t sit_sac_target_args_size(void);
+int sit_sac_target(sit_handle* h, const sit_sac_target_args* a, void* stream);
+int sit_sac_polyak(sit_handle* h, float* target, const float* online, int64_t n, float tau, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

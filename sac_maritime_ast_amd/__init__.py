@@ -9,7 +9,12 @@ from .replay import ReplayMemory, replay_reference
 
 __all__ = ["params", "params_from_reference", "Scenario", "make_scenario", "status_string",
            "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library", "EpisodeLog", "episodes_reference",
-           "ReplayMemory", "replay_reference"]
+           "ReplayMemory", "replay_reference", "QNetwork", "SacLearner", "SacUpdateReference",
+           "pack_critic_weights", "unpack_critic_weights", "sac_noise", "policy_noise", "sac_target_reference",
+           "sac_update_reference"]
+# the learner's names (sac.py imports torch: resolved on first use, like the env classes)
+_SAC = ("QNetwork", "SacLearner", "SacUpdateReference", "pack_critic_weights", "unpack_critic_weights", "sac_noise",
+        "policy_noise", "sac_target_reference", "sac_update_reference")
 
 
 def load_library():
@@ -23,4 +28,7 @@ def __getattr__(name):
     if name == "MultiShipRLEnv":
         from .compat import MultiShipRLEnv
         return MultiShipRLEnv
+    if name in _SAC:
+        from . import sac
+        return getattr(sac, name)
     raise AttributeError(name)

@@ -21,6 +21,10 @@ SIT_OBS_DIM = 10
 SIT_TRANSITION_DIM = 24
 SIT_ACTOR_HIDDEN = 256
 SIT_ACTOR_WEIGHTS = SIT_ACTOR_HIDDEN * SIT_OBS_DIM + SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN ** 2 + SIT_ACTOR_HIDDEN + 2 * SIT_ACTOR_HIDDEN + 2
+# one critic's packed block (11 -> 256 -> 256 -> 1), padded to a multiple of 4 floats
+SIT_CRITIC_INPUT = SIT_OBS_DIM + 1
+SIT_CRITIC_WEIGHTS = (SIT_ACTOR_HIDDEN * SIT_CRITIC_INPUT + SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN ** 2 + SIT_ACTOR_HIDDEN
+                      + SIT_ACTOR_HIDDEN + 1 + 3) // 4 * 4
 SIT_LOG_KEYS, SIT_LOG_ROWS = 27, 62
 SIT_EPISODE_ACTIONS, SIT_EPISODE_DIM = 14, 32
 INIT_FIELDS = ("north", "east", "yaw", "surge", "sway", "yaw_rate", "shaft_speed", "desired_speed",
@@ -113,6 +117,15 @@ class ReplaySampleArgs(ctypes.Structure):
     ]
 
 
+class SacTargetArgs(ctypes.Structure):
+    _fields_ = [
+        ("batch", c_int32), ("seed", c_uint64), ("update", c_uint64), ("gamma", c_double), ("reward_scale", c_double),
+        ("actor_weights", c_void_p), ("critic_weights", c_void_p), ("alpha", c_void_p),
+        ("next_state", c_void_p), ("reward", c_void_p), ("mask", c_void_p), ("y", c_void_p), ("noise", c_void_p),
+        ("next_action", c_void_p), ("next_logp", c_void_p), ("q1", c_void_p), ("q2", c_void_p),
+    ]
+
+
 class SitError(RuntimeError):
     pass
 
@@ -167,6 +180,9 @@ SIGNATURES = {
     "sit_replay_reserve": (c_int32, [c_void_p, c_int32, c_void_p]),
     "sit_replay_push": (c_int32, [c_void_p, POINTER(ReplayPushArgs), c_void_p]),
     "sit_replay_sample": (c_int32, [c_void_p, POINTER(ReplaySampleArgs), c_void_p]),
+    "sit_sac_target_args_size": (c_size_t, []),
+    "sit_sac_target": (c_int32, [c_void_p, POINTER(SacTargetArgs), c_void_p]),
+    "sit_sac_polyak": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p]),
 }
 
 _lib = None
@@ -198,7 +214,8 @@ def load():
     if hasattr(lib, "sit_episodes_args_size") and lib.sit_episodes_args_size() != ctypes.sizeof(EpisodesArgs):
         raise ImportError(f"sit_episodes_args layout mismatch: C {lib.sit_episodes_args_size()} vs "
                           f"ctypes {ctypes.sizeof(EpisodesArgs)} bytes")
-    for fn, struct in (("sit_replay_push_args_size", ReplayPushArgs), ("sit_replay_sample_args_size", ReplaySampleArgs)):
+    for fn, struct in (("sit_replay_push_args_size", ReplayPushArgs), ("sit_replay_sample_args_size", ReplaySampleArgs),
+                       ("sit_sac_target_args_size", SacTargetArgs)):
         if hasattr(lib, fn) and getattr(lib, fn)() != ctypes.sizeof(struct):
             raise ImportError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} vs ctypes {ctypes.sizeof(struct)} bytes")
     _lib = lib

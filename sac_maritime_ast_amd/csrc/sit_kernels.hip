@@ -7,6 +7,7 @@
 #include "sit_actor.h"
 #include "sit_episodes.h"
 #include "sit_replay.h"
+#include "sit_sac.h"
 
 #ifdef SIT_F32_TU
 int sit_launch_steps_f32(sit_handle* h, const void* io, void* stream);   // sit_steps_f32.hip
@@ -736,6 +737,21 @@ int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stre
   const size_t quad = 4 * real_size(h);
   if ((uintptr_t)a->ring % quad) return fail(h, SIT_E_INVALID, "replay: ring must be aligned to 4 reals (%zu bytes)", quad);
   return with_real(h, [&](auto t) { return replay_launch_sample<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+// ---- SAC learner (sit_sac.h) ---------------------------------------------------------------
+size_t sit_sac_target_args_size(void) { return sizeof(sit_sac_target_args); }
+
+int sit_sac_target(sit_handle* h, const sit_sac_target_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_target_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_target<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+int sit_sac_polyak(sit_handle* h, float* target, const float* online, int64_t n, float tau, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_polyak_args_error(target, online, n)) return fail(h, SIT_E_INVALID, "%s", why);
+  return sac_launch_polyak(h, target, online, n, tau, (hipStream_t)stream);
 }
 
 }  // extern "C"

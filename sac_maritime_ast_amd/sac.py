@@ -1,0 +1,458 @@
+"""The SAC learner: ``agent.update_parameters(memory, batch_size, updates)`` of
+``test_beds/main_ast.py:350-362``.
+
+The reference's ``ast_core/algorithms/sac.py`` is an empty file; ``main_ast.py:41-90`` fixes the
+algorithm: twin Q networks of hidden size 256, gamma 0.99, tau 0.005, lr 3e-4, alpha 0.2,
+automatic entropy tuning, target_update_interval 1, batch_size 64 -- standard SAC (Haarnoja et al.
+2018) with the actor of ``samplers.GaussianPolicy``.
+
+One update has two halves.  The gradient half (two critic losses, the policy loss, the temperature
+loss and their Adam steps) is PyTorch autograd.  The no-gradient half is inference only and is HIP
+(csrc/sit_sac.h, include/sit.h "SAC learner"): ``sit_sac_target`` evaluates the actor at next_state
+with its log-probability, both target critics at (next_state, a') and the TD target in one kernel, and
+``sit_sac_polyak`` moves the packed target block towards the online critics in another.
+``SacLearner(target="torch")`` computes the same formulas with PyTorch ops (the A/B, and the path for
+architectures ``pack_actor_weights`` / ``pack_critic_weights`` decline).
+
+``sac_target_reference`` is the executable specification of ``sit_sac_target`` in float64 NumPy,
+noise draw included; ``sac_update_reference`` is a whole update in float64 PyTorch on the CPU.
+
+Not included: HIP backward passes, graph capture of an update, prioritised replay, n-step returns,
+observation normalisation, multi-rank learners.
+"""
+from __future__ import annotations
+
+import copy
+import math
+from ctypes import byref, c_void_p
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from .replay import philox4x32_10
+from .samplers import EPS, LOG_SIG_CAP_MAX, LOG_SIG_CAP_MIN, pack_actor_weights
+
+OBS, H = _lib.SIT_OBS_DIM, _lib.SIT_ACTOR_HIDDEN
+CRITIC_IN = _lib.SIT_CRITIC_INPUT
+CRITIC_WEIGHTS = _lib.SIT_CRITIC_WEIGHTS
+TARGET_NOISE_TAG = 0x5441      # counter word 1 of sit_sac_target's draw
+POLICY_NOISE_TAG = 0x5049      # counter word 1 of the policy loss's draw
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+_M32 = 0xFFFFFFFF
+
+
+class QNetwork(nn.Module):
+    """Twin critic: two MLPs (obs + action) 11 -> 256 -> ReLU -> 256 -> ReLU -> 1 (main_ast.py:67,
+    ``hidden_size`` 256)."""
+
+    def __init__(self, obs_dim: int = OBS, act_dim: int = 1, hidden: int = H):
+        super().__init__()
+
+        def mlp():
+            return nn.Sequential(nn.Linear(obs_dim + act_dim, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(),
+                                 nn.Linear(hidden, 1))
+        self.q1, self.q2 = mlp(), mlp()
+
+    def forward(self, state: torch.Tensor, action: torch.Tensor):
+        x = torch.cat([state, action.reshape(state.shape[0], -1)], dim=-1)
+        return self.q1(x)[:, 0], self.q2(x)[:, 0]
+
+
+def _critic_layers(q: nn.Module):
+    """[(l1, l2, l3) of q1, of q2] when q is the twin 11 -> 256 -> 256 -> 1 ReLU critic, else None."""
+    out = []
+    for net in (getattr(q, "q1", None), getattr(q, "q2", None)):
+        if not isinstance(net, nn.Sequential) or len(net) != 5:
+            return None
+        l1, r1, l2, r2, l3 = net
+        ok = (all(isinstance(m, nn.Linear) and m.bias is not None for m in (l1, l2, l3))
+              and isinstance(r1, nn.ReLU) and isinstance(r2, nn.ReLU)
+              and tuple(l1.weight.shape) == (H, CRITIC_IN) and tuple(l2.weight.shape) == (H, H)
+              and tuple(l3.weight.shape) == (1, H))
+        if not ok:
+            return None
+        out.append((l1, l2, l3))
+    return out
+
+
+def _critic_segments(layers):
+    """(parameter view, shape in the block, offset) of both critics' blocks; W2 goes in transposed."""
+    for c, (l1, l2, l3) in enumerate(layers):
+        o = c * CRITIC_WEIGHTS
+        for t, shape in ((l1.weight, (H, CRITIC_IN)), (l1.bias, (H,)), (l2.weight.t(), (H, H)), (l2.bias, (H,)),
+                         (l3.weight, (1, H)), (l3.bias, (1,))):
+            yield t, shape, o
+            o += t.numel()
+
+
+def pack_critic_weights(q: nn.Module, out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The float32 block of sit_sac_target's critics (include/sit.h: two SIT_CRITIC_WEIGHTS blocks, Q1's
+    then Q2's, each W1 [256][11], b1, W2^T, b2, W3, b3 and zero padding to a multiple of 4 floats) from a
+    ``QNetwork``, or None for any other architecture.  With `out` the parameters are copied in place,
+    one copy per parameter; the padding is left as it is."""
+    layers = _critic_layers(q)
+    if layers is None:
+        return None
+    with torch.no_grad():
+        if out is None:
+            p = next(q.parameters())
+            out = torch.zeros(2 * CRITIC_WEIGHTS, dtype=torch.float32, device=p.device)
+        elif out.numel() != 2 * CRITIC_WEIGHTS or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"pack_critic_weights: out must be a contiguous float32 tensor of {2 * CRITIC_WEIGHTS} "
+                             f"elements (got {tuple(out.shape)} {out.dtype}, contiguous={out.is_contiguous()})")
+        flat = out.view(-1)
+        for t, shape, o in _critic_segments(layers):
+            flat[o:o + t.numel()].view(shape).copy_(t.detach())
+    return out
+
+
+def unpack_critic_weights(block: torch.Tensor, q: nn.Module) -> nn.Module:
+    """The inverse of ``pack_critic_weights``: the block's values into q's parameters."""
+    layers = _critic_layers(q)
+    if layers is None or block.numel() != 2 * CRITIC_WEIGHTS:
+        raise ValueError("unpack_critic_weights: a twin 11 -> 256 -> 256 -> 1 critic and its packed block are required")
+    with torch.no_grad():
+        flat = block.reshape(-1)
+        for t, shape, o in _critic_segments(layers):
+            t.copy_(flat[o:o + t.numel()].view(shape))
+    return q
+
+
+# ---------------------------------------------------------------------------------------------
+# noise: Philox4x32-10 and the Box-Muller step of the policy's event noise (csrc/sit_device.h)
+# ---------------------------------------------------------------------------------------------
+def sac_noise(seed: int, rows, update: int, tag: int = TARGET_NOISE_TAG) -> np.ndarray:
+    """Standard normals (float64) of Philox4x32-10(key = seed, ctr = (row, tag, update lo, update hi)):
+    u1 in (0, 1] and u2 in [0, 1) from 53 bits each, sqrt(-2 log u1) cos(2 pi u2).  tag 0x5441 is
+    sit_sac_target's device draw."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    seed, update = int(seed) & 0xFFFFFFFFFFFFFFFF, int(update) & 0xFFFFFFFFFFFFFFFF
+    full = lambda v: np.full(rows.shape, v, dtype=np.uint64)  # noqa: E731
+    c = philox4x32_10((rows, full(tag), full(update & _M32), full(update >> 32)), (seed & _M32, seed >> 32))
+    f = [x.astype(np.float64) for x in ((c[0] >> np.uint32(5)), (c[1] >> np.uint32(6)), (c[2] >> np.uint32(5)),
+                                        (c[3] >> np.uint32(6)))]
+    u1 = (f[0] * 67108864.0 + f[1] + 1.0) * (1.0 / 9007199254740992.0)
+    u2 = (f[2] * 67108864.0 + f[3]) * (1.0 / 9007199254740992.0)
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def policy_noise(seed: int, update: int, batch: int) -> np.ndarray:
+    """The policy loss's reparameterisation noise of one update: float64 [batch], a function of
+    (seed, update) that a device learner and a reference learner share."""
+    return sac_noise(seed, np.arange(batch), update, POLICY_NOISE_TAG)
+
+
+# ---------------------------------------------------------------------------------------------
+# the specification of sit_sac_target
+# ---------------------------------------------------------------------------------------------
+def _mlp64(w: np.ndarray, n_in: int, n_out: int, x: np.ndarray) -> np.ndarray:
+    """A packed (n_in -> 256 -> 256 -> n_out) block applied to x [B, n_in] in float64."""
+    w = np.asarray(w, dtype=np.float64)
+    o = 0
+    w1 = w[o:o + H * n_in].reshape(H, n_in); o += H * n_in
+    b1 = w[o:o + H]; o += H
+    w2t = w[o:o + H * H].reshape(H, H); o += H * H
+    b2 = w[o:o + H]; o += H
+    w3 = w[o:o + n_out * H].reshape(n_out, H); o += n_out * H
+    b3 = w[o:o + n_out]
+    h = np.maximum(x @ w1.T + b1, 0.0)
+    h = np.maximum(h @ w2t + b2, 0.0)
+    return h @ w3.T + b3
+
+
+def log_one_minus_tanh_sq(x):
+    """log(1 - tanh(x)^2 + 1e-6) from x without cancellation: 1 - tanh(x)^2 = 4 (em + 1) / (em + 2)^2 with
+    em = expm1(2 |x|).  (1 - a * a with a = tanh(x) loses every digit once a rounds to 1.)  NumPy arrays
+    or torch tensors, in their own precision."""
+    if isinstance(x, torch.Tensor):
+        em = torch.expm1(2.0 * x.abs().clamp(max=40.0))
+        rc = 1.0 / (em + 2.0)
+        return torch.log(4.0 * ((em + 1.0) * rc) * rc + EPS)
+    em = np.expm1(2.0 * np.minimum(np.abs(x), 300.0))
+    rc = 1.0 / (em + 2.0)
+    return np.log(4.0 * ((em + 1.0) * rc) * rc + EPS)
+
+
+def sac_target_reference(actor_weights, critic_weights, next_state, reward, mask, *, alpha: float, gamma: float,
+                         reward_scale: float = 1.0, noise=None, seed: int = 0, update: int = 0) -> dict:
+    """sit_sac_target (include/sit.h "SAC learner") in float64 NumPy, from the packed float32 blocks.
+    noise None: the device draw, ``sac_noise(seed, row, update)``.  Returns y, next_action, next_logp, q1,
+    q2 (and noise, x: the draw and the pre-squash sample), each float64 [B]."""
+    as64 = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)  # noqa: E731
+    aw, cw = as64(actor_weights).reshape(-1), as64(critic_weights).reshape(-1)
+    if aw.size != _lib.SIT_ACTOR_WEIGHTS or cw.size != 2 * CRITIC_WEIGHTS:
+        raise ValueError("sac_target_reference: packed actor and two-critic blocks are required")
+    ns = as64(next_state).reshape(-1, OBS)
+    B = ns.shape[0]
+    reward, mask = as64(reward).reshape(B), as64(mask).reshape(B)
+    eps = sac_noise(seed, np.arange(B), update) if noise is None else as64(noise).reshape(B)
+    head = _mlp64(aw, OBS, 2, ns)
+    mu, ls = head[:, 0], np.clip(head[:, 1], LOG_SIG_CAP_MIN, LOG_SIG_CAP_MAX)
+    x = np.exp(ls) * eps + mu
+    a = np.tanh(x)
+    logp = -0.5 * eps * eps - ls - HALF_LOG_2PI - log_one_minus_tanh_sq(x)
+    xin = np.concatenate([ns, a[:, None]], axis=1)
+    q1 = _mlp64(cw[:CRITIC_WEIGHTS], CRITIC_IN, 1, xin)[:, 0]
+    q2 = _mlp64(cw[CRITIC_WEIGHTS:], CRITIC_IN, 1, xin)[:, 0]
+    y = reward_scale * reward + mask * gamma * (np.minimum(q1, q2) - float(alpha) * logp)
+    return {"y": y, "next_action": a, "next_logp": logp, "q1": q1, "q2": q2, "noise": eps, "x": x}
+
+
+def torch_target(policy, target_critic, next_state, reward, mask, eps, alpha, gamma, reward_scale=1.0) -> dict:
+    """The formulas of sit_sac_target with PyTorch ops, in the dtype and on the device of the networks
+    and inputs (no gradients): y, next_action, next_logp, q1, q2."""
+    with torch.no_grad():
+        head = policy.net(next_state)
+        mu, ls = head[:, 0], head[:, 1].clamp(LOG_SIG_CAP_MIN, LOG_SIG_CAP_MAX)
+        x = torch.addcmul(mu, ls.exp(), eps)
+        a = torch.tanh(x)
+        logp = -0.5 * eps * eps - ls - HALF_LOG_2PI - log_one_minus_tanh_sq(x)
+        q1, q2 = target_critic(next_state, a[:, None])
+        y = reward_scale * reward + mask * gamma * (torch.min(q1, q2) - alpha * logp)
+        return {"y": y, "next_action": a, "next_logp": logp, "q1": q1, "q2": q2}
+
+
+def _torch_target(*args):
+    return torch_target(*args)["y"]
+
+
+def _sample(memory, batch_size):
+    """One minibatch of a ReplayMemory (device tensors) or a ReplayReference (NumPy) as [B, ...] items."""
+    b = memory.sample(batch_size)
+    return {k: b[k][0] for k in ("state", "action", "reward", "next_state", "mask")}
+
+
+def _gradient_half(pol, critic, optims, log_alpha, alpha, auto, batch, y, eps_pi, target_entropy=-1.0):
+    """The gradient half of one update, shared by the learner and the float64 reference: the two critic
+    MSE losses and their Adam step, the policy loss mean(alpha logp - min(Q1, Q2)(s, pi(s))) and its
+    step, the temperature loss -mean(log_alpha (logp + target_entropy).detach()) and its step.
+    Returns the four losses (tensors) and the new alpha (a tensor when tuned)."""
+    state, action = batch["state"], batch["action"]
+    q1, q2 = critic(state, action)
+    l1, l2 = nn.functional.mse_loss(q1, y), nn.functional.mse_loss(q2, y)
+    optims["critic"].zero_grad(set_to_none=True)
+    (l1 + l2).backward()
+    optims["critic"].step()
+    pi, logp, _, _ = pol(state, eps_pi[:, None])
+    q1p, q2p = critic(state, pi)
+    lp = (alpha * logp - torch.min(q1p, q2p)).mean()
+    optims["policy"].zero_grad(set_to_none=True)
+    lp.backward()
+    optims["policy"].step()
+    if auto:
+        la = -(log_alpha * (logp + target_entropy).detach()).mean()
+        optims["alpha"].zero_grad(set_to_none=True)
+        la.backward()
+        optims["alpha"].step()
+        alpha = log_alpha.detach().exp()
+    else:
+        la = torch.zeros((), dtype=l1.dtype, device=l1.device)
+    return l1.detach(), l2.detach(), lp.detach(), la.detach(), alpha
+
+
+class SacLearner:
+    """SAC updates on the device of one ``VecMultiShipRLEnv`` from its ``ReplayMemory``.
+
+    `policy` is the ``GaussianPolicy`` the samplers serve (float32, on the env's device); the learner
+    owns the twin critic (``critic``: a ``QNetwork`` to start from, default a fresh one), the target
+    critics (copies of the online critics at construction), the three Adam optimisers and log_alpha.
+    target="hip": the no-gradient half is ``sit_sac_target`` / ``sit_sac_polyak`` and the targets live
+    only as the packed block ``target_weights``; it needs the reference's architectures
+    (``pack_actor_weights`` / ``pack_critic_weights``) and raises for others -- pick target="torch" for
+    those, which computes the same formulas with PyTorch ops on a target ``QNetwork``.
+
+    ``actor_weights`` is the packed actor block sit_sac_target reads, repacked in place at the end of
+    every update.  A ``PolicySampler`` built on the same `policy` keeps a block of its own: call its
+    ``refresh_weights()`` after an update (its ``launch()`` does so by itself when the parameters
+    changed, except inside a HIP-graph replay)."""
+
+    def __init__(self, env, policy: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
+                 alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
+                 reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None):
+        if target not in ("hip", "torch"):
+            raise ValueError("target must be 'hip' or 'torch'")
+        self.env, self.policy, self.target = env, policy, target
+        self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
+        self.target_update_interval, self.seed = int(target_update_interval), int(seed)
+        self.auto = bool(automatic_entropy_tuning)
+        dev = env.device
+        self.critic = (critic if critic is not None else QNetwork()).to(device=dev, dtype=torch.float32)
+        self.log_alpha = torch.full((1,), math.log(alpha), dtype=torch.float32, device=dev, requires_grad=self.auto)
+        self.alpha = self.log_alpha.detach().exp()           # float32[1] on the device: sit_sac_target reads it there
+        self.optims = {"critic": torch.optim.Adam(self.critic.parameters(), lr=lr),
+                       "policy": torch.optim.Adam(self.policy.parameters(), lr=lr)}
+        if self.auto:
+            self.optims["alpha"] = torch.optim.Adam([self.log_alpha], lr=lr)
+        self._ready = False
+        self._out = {}
+        if target == "hip":
+            self.actor_weights = pack_actor_weights(policy)
+            self.online_weights = pack_critic_weights(self.critic)
+            if self.actor_weights is None or self.online_weights is None:
+                raise ValueError("target='hip' needs the reference's actor (10 -> 256 -> 256 -> 2) and twin critic "
+                                 "(11 -> 256 -> 256 -> 1); use target='torch' for other architectures")
+            if self.actor_weights.device != dev or self.actor_weights.dtype != torch.float32:
+                raise ValueError(f"target='hip' needs a float32 policy on {dev}")
+            self.target_weights = self.online_weights.clone()
+            self.target_critic = None
+        else:
+            self.actor_weights = pack_actor_weights(policy)      # None for other architectures
+            self.online_weights = self.target_weights = None
+            self.target_critic = copy.deepcopy(self.critic).requires_grad_(False)
+
+    # ---------------- the no-gradient half ----------------
+    def td_target(self, next_state, reward, mask, update: int, noise=None, diagnostics: dict | None = None):
+        """y [B] (the env's real type) of one minibatch through sit_sac_target; noise None draws on the
+        device.  diagnostics: a dict that receives next_action, next_logp, q1, q2."""
+        B = int(next_state.shape[0])
+        dt, dev = self.env.dtype, self.env.device
+        y = self._out.get(B)
+        if y is None:
+            y = self._out[B] = torch.empty(B, dtype=dt, device=dev)
+        a = _lib.SacTargetArgs()
+        a.batch, a.seed, a.update = B, self.seed & 0xFFFFFFFFFFFFFFFF, int(update) & 0xFFFFFFFFFFFFFFFF
+        a.gamma, a.reward_scale = self.gamma, self.reward_scale
+        a.actor_weights, a.critic_weights = self.actor_weights.data_ptr(), self.target_weights.data_ptr()
+        a.alpha = self.alpha.data_ptr()
+        for name, t in (("next_state", next_state), ("reward", reward), ("mask", mask)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous {dt} tensor on {dev} is required")
+            setattr(a, name, t.data_ptr())
+        a.y = y.data_ptr()
+        a.noise = None if noise is None else noise.data_ptr()
+        if diagnostics is not None:
+            for k in ("next_action", "next_logp", "q1", "q2"):
+                diagnostics[k] = torch.empty(B, dtype=dt, device=dev)
+                setattr(a, k, diagnostics[k].data_ptr())
+        with torch.cuda.device(dev):
+            self.env._call("sit_sac_target", byref(a), self.env._stream())
+        return y
+
+    def _host_noise(self, values: np.ndarray):
+        return torch.from_numpy(values.astype(np.float32)).to(self.env.device, non_blocking=True)
+
+    def _polyak(self):
+        if self.target == "hip":
+            pack_critic_weights(self.critic, out=self.online_weights)
+            with torch.cuda.device(self.env.device):
+                self.env._call("sit_sac_polyak", c_void_p(self.target_weights.data_ptr()),
+                               c_void_p(self.online_weights.data_ptr()), self.online_weights.numel(), self.tau,
+                               self.env._stream())
+        else:
+            with torch.no_grad():
+                for t, p in zip(self.target_critic.parameters(), self.critic.parameters()):
+                    t.add_(p - t, alpha=self.tau)
+
+    # ---------------- one update ----------------
+    def update_parameters(self, memory, batch_size: int, updates: int):
+        """One SAC update from one minibatch of `memory`; `updates` is the caller's update counter
+        (main_ast.py:350-362).  Returns (critic_1_loss, critic_2_loss, policy_loss, ent_loss, alpha) as
+        floats, or None while len(memory) <= batch_size (nothing is done then)."""
+        B = int(batch_size)
+        if not self._ready:
+            if len(memory) <= B:
+                return None
+            self._ready = True        # a ring never shrinks
+        raw = _sample(memory, B)
+        if self.target == "hip":
+            y = self.td_target(raw["next_state"], raw["reward"], raw["mask"], updates).to(torch.float32)
+            batch = {k: v.to(torch.float32) for k, v in raw.items()}
+        else:
+            batch = {k: v.to(torch.float32) for k, v in raw.items()}
+            eps = self._host_noise(sac_noise(self.seed, np.arange(B), updates))
+            y = _torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
+                              self.alpha, self.gamma, self.reward_scale)
+        eps_pi = self._host_noise(policy_noise(self.seed, updates, B))
+        l1, l2, lp, la, alpha = _gradient_half(self.policy, self.critic, self.optims, self.log_alpha, self.alpha,
+                                               self.auto, batch, y, eps_pi)
+        if self.auto:
+            self.alpha.copy_(alpha)
+        if updates % self.target_update_interval == 0:
+            self._polyak()
+        if self.actor_weights is not None:
+            pack_actor_weights(self.policy, out=self.actor_weights)
+        return tuple(torch.stack([l1, l2, lp, la.reshape(()), self.alpha[0]]).tolist())
+
+    # ---------------- checkpoint ----------------
+    def state_dict(self) -> dict:
+        """Networks, optimisers, targets (as the packed block, in both modes) and log_alpha."""
+        tw = self.target_weights if self.target == "hip" else pack_critic_weights(self.target_critic)
+        return {"policy": copy.deepcopy(self.policy.state_dict()), "critic": copy.deepcopy(self.critic.state_dict()),
+                "critic_target": None if tw is None else tw.clone(),
+                "critic_target_state": None if tw is not None else copy.deepcopy(self.target_critic.state_dict()),
+                "log_alpha": self.log_alpha.detach().clone(),
+                "optims": {k: copy.deepcopy(o.state_dict()) for k, o in self.optims.items()}}
+
+    def load_state_dict(self, sd: dict):
+        self.policy.load_state_dict(sd["policy"])
+        self.critic.load_state_dict(sd["critic"])
+        if self.target == "hip":
+            if sd.get("critic_target") is None:
+                raise ValueError("this checkpoint holds no packed target block")
+            self.target_weights.copy_(sd["critic_target"])
+            pack_critic_weights(self.critic, out=self.online_weights)
+        elif sd.get("critic_target") is not None:
+            unpack_critic_weights(sd["critic_target"].to(self.env.device), self.target_critic)
+        else:
+            self.target_critic.load_state_dict(sd["critic_target_state"])
+        with torch.no_grad():
+            self.log_alpha.copy_(sd["log_alpha"])
+            self.alpha.copy_(self.log_alpha.detach().exp())
+        for k, o in self.optims.items():
+            o.load_state_dict(sd["optims"][k])
+        if self.actor_weights is not None:
+            pack_actor_weights(self.policy, out=self.actor_weights)
+
+
+class SacUpdateReference:
+    """``SacLearner``'s update in float64 PyTorch on the CPU: deep copies of the networks, a target
+    ``QNetwork``, the TD target by the formulas of ``sac_target_reference`` and the same noise draws."""
+
+    def __init__(self, policy: nn.Module, critic: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
+                 alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
+                 reward_scale: float = 1.0, seed: int = 25450):
+        self.policy = copy.deepcopy(policy).to(device="cpu", dtype=torch.float64)
+        self.critic = copy.deepcopy(critic).to(device="cpu", dtype=torch.float64)
+        self.target_critic = copy.deepcopy(self.critic).requires_grad_(False)
+        self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
+        self.target_update_interval, self.seed = int(target_update_interval), int(seed)
+        self.auto = bool(automatic_entropy_tuning)
+        self.log_alpha = torch.full((1,), math.log(alpha), dtype=torch.float64, requires_grad=self.auto)
+        self.alpha = self.log_alpha.detach().exp()
+        self.optims = {"critic": torch.optim.Adam(self.critic.parameters(), lr=lr),
+                       "policy": torch.optim.Adam(self.policy.parameters(), lr=lr)}
+        if self.auto:
+            self.optims["alpha"] = torch.optim.Adam([self.log_alpha], lr=lr)
+
+    def update_parameters(self, memory, batch_size: int, updates: int):
+        B = int(batch_size)
+        if len(memory) <= B:
+            return None
+        as64 = lambda v: (v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))).to(torch.float64)  # noqa: E731
+        batch = {k: as64(v) for k, v in _sample(memory, B).items()}
+        eps = torch.from_numpy(sac_noise(self.seed, np.arange(B), updates))
+        y = _torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
+                          self.alpha, self.gamma, self.reward_scale)
+        eps_pi = torch.from_numpy(policy_noise(self.seed, updates, B))
+        l1, l2, lp, la, alpha = _gradient_half(self.policy, self.critic, self.optims, self.log_alpha, self.alpha,
+                                               self.auto, batch, y, eps_pi)
+        if self.auto:
+            self.alpha = alpha
+        if updates % self.target_update_interval == 0:
+            with torch.no_grad():
+                for t, p in zip(self.target_critic.parameters(), self.critic.parameters()):
+                    t.add_(p - t, alpha=self.tau)
+        return float(l1), float(l2), float(lp), float(la), float(self.alpha[0])
+
+
+def sac_update_reference(policy: nn.Module, critic: nn.Module, **kw) -> SacUpdateReference:
+    """A float64 CPU learner with ``SacLearner``'s update (``SacUpdateReference``), started from copies of
+    `policy` and `critic`."""
+    return SacUpdateReference(policy, critic, **kw)
+
+
+__all__ = ["QNetwork", "SacLearner", "SacUpdateReference", "pack_critic_weights",
+           "unpack_critic_weights", "sac_noise", "policy_noise", "log_one_minus_tanh_sq", "sac_target_reference", "torch_target",
+           "sac_update_reference"]

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Cost of the SAC learner's no-gradient half: the fused HIP path next to PyTorch (GPU).
+
+    python3 tools/sac_cost.py [--calls 30] [--warmup 5] [out.json]
+
+float32 handle of 64 envs, the reference's networks (actor 10-256-256-2, twin critic 11-256-256-1,
+default initialisation), a ring of 4096 synthetic normalised records.  Every figure is the median of
+`calls` HIP-event spans after `warmup` calls, the alternatives interleaved call by call on one stream:
+
+  target   sit_sac_target against the same formulas as PyTorch ops without gradients (torch_target; its
+           noise by torch.randn on the device), at B = 64, 256, 4096
+  polyak   sit_sac_polyak on the packed two-critic block (alone, and with the in-place repack of the online
+           critics that precedes it in SacLearner) against the per-parameter update t += tau (p - t)
+  update   a whole SacLearner.update_parameters at batch 64 with target="hip" and target="torch" (each
+           ends with the host reading the five results, so the span is also the wall time)
+
+and the share of an update the no-gradient half takes (target + Polyak over the update).  There is no
+pass threshold; the result goes to profiles/r08_sac_cost.json."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "r08_sac_cost.json"))
+    a = ap.parse_args()
+    if a.calls < 20:
+        ap.error("time at least 20 calls")
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("sac_cost: needs a GPU (a CPU run gives no time)")
+    from sac_maritime_ast_amd import ReplayMemory, VecMultiShipRLEnv, _lib, make_scenario, sac
+    from sac_maritime_ast_amd.samplers import GaussianPolicy
+
+    dev = "cuda:0"
+    env = VecMultiShipRLEnv(scenario=make_scenario(64), precision=32, device=dev)
+    torch.manual_seed(0)
+    pol0, q0 = GaussianPolicy(), sac.QNetwork()
+
+    def learner(target):
+        return sac.SacLearner(env, copy.deepcopy(pol0).to(dev), critic=copy.deepcopy(q0), target=target, seed=1)
+
+    def memory():
+        mem = ReplayMemory(env, 4096, seed=1)
+        g = torch.Generator(device=dev).manual_seed(2)
+        mem.ring.copy_(torch.randn(mem.ring.shape, generator=g, device=dev))
+        mem.ring[:, 10].tanh_()
+        mem.ring[:, 22] = (mem.ring[:, 22] > -0.7).to(mem.ring.dtype)
+        mem.cursor[0] = 4096
+        return mem
+
+    hip, tor = learner("hip"), learner("torch")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def span(fn):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) * 1e3     # microseconds
+
+    def interleaved(fns):
+        """{name: median us} of the named calls, run in turn `warmup + calls` times."""
+        t = {k: [] for k in fns}
+        for i in range(a.warmup + a.calls):
+            for k, fn in fns.items():
+                us = span(fn)
+                if i >= a.warmup:
+                    t[k].append(us)
+        return {k: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for k, v in t.items()}
+
+    res = {"what": __doc__.split("\n\n")[0], "calls": a.calls, "warmup": a.warmup,
+           "device": torch.cuda.get_device_name(0), "target": {}, "polyak": {}, "update": {}}
+    # ---- target ----
+    for B in (64, 256, 4096):
+        ns = torch.randn(B, _lib.SIT_OBS_DIM, device=dev)
+        reward, mask = torch.randn(B, device=dev), torch.ones(B, device=dev)
+
+        def by_torch():
+            eps = torch.randn(B, device=dev)
+            return sac.torch_target(tor.policy, tor.target_critic, ns, reward, mask, eps, tor.alpha, tor.gamma)["y"]
+        r = interleaved({"hip": lambda: hip.td_target(ns, reward, mask, 7), "torch": by_torch})
+        r["torch_over_hip"] = r["torch"]["median_us"] / r["hip"]["median_us"]
+        res["target"][str(B)] = r
+    # ---- polyak ----
+    def hip_kernel():
+        with torch.cuda.device(env.device):
+            env._call("sit_sac_polyak", hip.target_weights.data_ptr(), hip.online_weights.data_ptr(),
+                      hip.online_weights.numel(), hip.tau, env._stream())
+    r = interleaved({"hip_kernel": hip_kernel, "hip_repack_and_kernel": hip._polyak, "torch": tor._polyak})
+    r["torch_over_hip_repack_and_kernel"] = r["torch"]["median_us"] / r["hip_repack_and_kernel"]["median_us"]
+    res["polyak"] = r
+    # ---- a whole update ----
+    mems = {"hip": memory(), "torch": memory()}
+    count = {"hip": 0, "torch": 0}
+    wall = {"hip": [], "torch": []}
+
+    def update(mode, lrn):
+        def fn():
+            t0 = time.perf_counter()
+            out = lrn.update_parameters(mems[mode], 64, count[mode])
+            wall[mode].append((time.perf_counter() - t0) * 1e6)
+            count[mode] += 1
+            assert out is not None
+        return fn
+    r = interleaved({"hip": update("hip", hip), "torch": update("torch", tor)})
+    for mode in ("hip", "torch"):
+        r[mode]["wall_median_us"] = statistics.median(wall[mode][a.warmup:])
+    r["torch_over_hip"] = r["torch"]["median_us"] / r["hip"]["median_us"]
+    res["update"] = r
+    t64 = res["target"]["64"]
+    res["no_grad_share_of_update"] = {
+        "hip": (t64["hip"]["median_us"] + res["polyak"]["hip_repack_and_kernel"]["median_us"]) / r["hip"]["median_us"],
+        "torch": (t64["torch"]["median_us"] + res["polyak"]["torch"]["median_us"]) / r["torch"]["median_us"]}
+    res["faster_update_at_batch_64"] = "hip" if r["hip"]["median_us"] <= r["torch"]["median_us"] else "torch"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
