@@ -634,6 +634,101 @@ size_t sit_sac_target_args_size(void);
 int sit_sac_target(sit_handle* h, const sit_sac_target_args* a, void* stream);
 int sit_sac_polyak(sit_handle* h, float* target, const float* online, int64_t n, float tau, void* stream);
 
+/* ---- SAC learner: the gradient half of an update -------------------------------------
+ * The two critic losses, the policy loss and the temperature loss of agent.update_parameters with their
+ * backward passes and Adam steps, for the architectures above (actor 10 -> 256 -> 256 -> 2, twin critic
+ * 11 -> 256 -> 256 -> 1).  Two calls of two kernels each on the caller's stream (forward + backward per
+ * row, then the weight gradients fused with Adam); a whole update is sit_sac_target, sit_sac_critic_step,
+ * sit_sac_policy_step, sit_sac_polyak.  Networks, gradients and Adam moments are float32; the minibatch
+ * arrays are in the handle's real type.  Both calls validate their arguments (SIT_E_INVALID for a null
+ * required pointer, batch <= 0, a parameter or moment block that is not 16-byte aligned, or a workspace
+ * smaller than sit_sac_workspace_floats(batch): nothing is launched), allocate nothing and never
+ * synchronise.  Every sum has a fixed order and there are no atomics: the same state gives the same bits.
+ * The means over the rows that form the results (and the temperature's gradient) are summed in float64,
+ * ascending, and rounded to float32 once.
+ *
+ * One network's backward pass, from its output gradients g[b][o], with x the input row, h1, h2 the hidden
+ * activations and z2[n] = sum_k W2T[k][n] h1[k] + b2[n]:
+ *   dW3[o] = sum_b g[b][o] h2[b];  db3[o] = sum_b g[b][o]
+ *   d2 = (sum_o W3[o] g[o]) * [h2 > 0];  dW2T[k][n] = sum_b h1[b][k] d2[b][n];  db2 = sum_b d2
+ *   d1[k] = (sum_n W2T[k][n] d2[n]) * [h1[k] > 0];  dW1[j][i] = sum_b d1[b][j] x[b][i];  db1 = sum_b d1
+ * each sum over b ascending.  Adam (torch defaults; `bias1` = 1 - beta1^t, `bias2` = 1 - beta2^t of the
+ * step count t the caller keeps, formed in double on the host), per element with gradient g:
+ *   m <- m + (1 - beta1) (g - m);  v <- beta2 v + (1 - beta2) g^2
+ *   p <- p - (lr / bias1) m / (sqrt(v) / sqrt(bias2) + eps)
+ * applied in place to the packed block and its moment blocks of the same layout; padding floats are not
+ * touched.  The gradient is never stored.
+ *
+ * sit_sac_critic_step, B = batch, x = concat(state, action), y from sit_sac_target, for i = 1, 2:
+ *   q_i = Q_i(x);  l_i = mean_b (q_i - y)^2;  g_i[b] = 2 (q_i[b] - y[b]) / B
+ * then one Adam step on both critics.  results[0], results[1] = l_1, l_2.
+ *
+ * sit_sac_policy_step, with the critics as they are (just updated) and alpha as it is before this call:
+ *   (mu, ls_raw) = actor(state);  ls = clip(ls_raw, -20, 2)
+ *   eps = noise[b], or the draw of sit_sac_target with counter word 1 = 0x5049
+ *   x = fma(exp(ls), eps, mu);  a = tanh(x);  s = 1 - tanh(x)^2 = 4 (em + 1) / (em + 2)^2, em = expm1(2 |x|)
+ *   logp = -0.5 eps^2 - ls - 0.5 log(2 pi) - log(s + 1e-6)
+ *   q_i = Q_i(concat(state, a));  lp = mean_b (alpha logp - min(q1, q2))
+ * backward: the critic with the smaller q (q1 on a tie) is seeded with -1/B and taken through to input
+ * column 10 only, g_a = sum_j W1[j][10] d1[j] (no critic parameter gradient is formed);
+ *   dx = (alpha / B) 2 a s / (s + 1e-6) + g_a s;  dmu = dx
+ *   dls = dx exp(ls) eps - alpha / B, and 0 where ls_raw lies outside [-20, 2] (the bounds pass it)
+ * then the actor's backward pass with the two output gradients (dmu, dls) and one Adam step on the actor.
+ * Temperature, when tune != 0 (log_alpha as it is before this call):
+ *   la = -mean_b (log_alpha (logp + target_entropy));  d la / d log_alpha = -mean_b (logp + target_entropy)
+ *   one scalar Adam step on log_alpha (alpha_adam), then alpha[0] = exp(log_alpha)
+ * tune == 0: la = 0, alpha and log_alpha are untouched.  results[2..4] = lp, la, alpha[0] after the call.
+ *
+ * Workspace: float32, sit_sac_workspace_floats(batch) = 2 * batch * SIT_SAC_WORKSPACE_ROW elements, where
+ * the row kernels leave each row's input, h1, h2, d1, d2, output gradients and loss terms for the Adam
+ * kernels.  The two calls may share one workspace. */
+#define SIT_SAC_WORKSPACE_ROW 1040
+typedef struct sit_sac_adam {
+  double lr, beta1, beta2, eps;
+  double bias1;                /* 1 - beta1^t */
+  double bias2;                /* 1 - beta2^t */
+} sit_sac_adam;
+typedef struct sit_sac_critic_step_args {
+  int32_t batch;               /* rows B, > 0 */
+  int64_t workspace_floats;    /* elements of workspace, >= sit_sac_workspace_floats(batch) */
+  sit_sac_adam adam;
+  float* critic_weights;       /* float[2][SIT_CRITIC_WEIGHTS] (the online critics), 16-byte aligned */
+  float* critic_m;             /* first moments, the same layout, 16-byte aligned */
+  float* critic_v;             /* second moments */
+  const void* state;           /* real[B][10] */
+  const void* action;          /* real[B] */
+  const void* y;               /* real[B] */
+  float* workspace;
+  float* results;              /* float[5]: [0], [1] are written */
+} sit_sac_critic_step_args;
+typedef struct sit_sac_policy_step_args {
+  int32_t batch;               /* rows B, > 0 */
+  int32_t tune;                /* != 0: the temperature step */
+  int64_t workspace_floats;
+  uint64_t seed;               /* key of the noise draw (noise == NULL) */
+  uint64_t update;             /* counter words 2, 3 of the noise draw */
+  double target_entropy;
+  sit_sac_adam adam;           /* the actor's */
+  sit_sac_adam alpha_adam;     /* log_alpha's (tune != 0) */
+  float* actor_weights;        /* float[SIT_ACTOR_WEIGHTS], 16-byte aligned */
+  float* actor_m;
+  float* actor_v;
+  const float* critic_weights; /* float[2][SIT_CRITIC_WEIGHTS], read only, 16-byte aligned */
+  float* alpha;                /* float[1], device; written when tune != 0 */
+  float* log_alpha;            /* float[1] and its two moments: required when tune != 0 */
+  float* log_alpha_m;
+  float* log_alpha_v;
+  const void* state;           /* real[B][10] */
+  const void* noise;           /* real[B] or NULL (drawn on the device) */
+  float* workspace;
+  float* results;              /* float[5]: [2], [3], [4] are written */
+} sit_sac_policy_step_args;
+int64_t sit_sac_workspace_floats(int32_t batch);   /* 0 for batch <= 0 */
+size_t sit_sac_critic_step_args_size(void);
+size_t sit_sac_policy_step_args_size(void);
+int sit_sac_critic_step(sit_handle* h, const sit_sac_critic_step_args* a, void* stream);
+int sit_sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,10 +11,11 @@ __all__ = ["params", "params_from_reference", "Scenario", "make_scenario", "stat
            "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library", "EpisodeLog", "episodes_reference",
            "ReplayMemory", "replay_reference", "QNetwork", "SacLearner", "SacUpdateReference",
            "pack_critic_weights", "unpack_critic_weights", "sac_noise", "policy_noise", "sac_target_reference",
-           "sac_update_reference"]
+           "sac_update_reference", "bind_parameters", "block_views", "moments_to_adam_state", "adam_state_to_moments"]
 # the learner's names (sac.py imports torch: resolved on first use, like the env classes)
 _SAC = ("QNetwork", "SacLearner", "SacUpdateReference", "pack_critic_weights", "unpack_critic_weights", "sac_noise",
-        "policy_noise", "sac_target_reference", "sac_update_reference")
+        "policy_noise", "sac_target_reference", "sac_update_reference", "bind_parameters", "block_views",
+        "moments_to_adam_state", "adam_state_to_moments")
 
 
 def load_library():

@@ -25,6 +25,7 @@ SIT_ACTOR_WEIGHTS = SIT_ACTOR_HIDDEN * SIT_OBS_DIM + SIT_ACTOR_HIDDEN + SIT_ACTO
 SIT_CRITIC_INPUT = SIT_OBS_DIM + 1
 SIT_CRITIC_WEIGHTS = (SIT_ACTOR_HIDDEN * SIT_CRITIC_INPUT + SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN ** 2 + SIT_ACTOR_HIDDEN
                       + SIT_ACTOR_HIDDEN + 1 + 3) // 4 * 4
+SIT_SAC_WORKSPACE_ROW = 1040   # floats per row and network pass of the gradient half's workspace
 SIT_LOG_KEYS, SIT_LOG_ROWS = 27, 62
 SIT_EPISODE_ACTIONS, SIT_EPISODE_DIM = 14, 32
 INIT_FIELDS = ("north", "east", "yaw", "surge", "sway", "yaw_rate", "shaft_speed", "desired_speed",
@@ -126,6 +127,29 @@ class SacTargetArgs(ctypes.Structure):
     ]
 
 
+class SacAdam(ctypes.Structure):
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("bias1", c_double),
+                ("bias2", c_double)]
+
+
+class SacCriticStepArgs(ctypes.Structure):
+    _fields_ = [
+        ("batch", c_int32), ("workspace_floats", c_int64), ("adam", SacAdam),
+        ("critic_weights", c_void_p), ("critic_m", c_void_p), ("critic_v", c_void_p),
+        ("state", c_void_p), ("action", c_void_p), ("y", c_void_p), ("workspace", c_void_p), ("results", c_void_p),
+    ]
+
+
+class SacPolicyStepArgs(ctypes.Structure):
+    _fields_ = [
+        ("batch", c_int32), ("tune", c_int32), ("workspace_floats", c_int64), ("seed", c_uint64), ("update", c_uint64),
+        ("target_entropy", c_double), ("adam", SacAdam), ("alpha_adam", SacAdam),
+        ("actor_weights", c_void_p), ("actor_m", c_void_p), ("actor_v", c_void_p), ("critic_weights", c_void_p),
+        ("alpha", c_void_p), ("log_alpha", c_void_p), ("log_alpha_m", c_void_p), ("log_alpha_v", c_void_p),
+        ("state", c_void_p), ("noise", c_void_p), ("workspace", c_void_p), ("results", c_void_p),
+    ]
+
+
 class SitError(RuntimeError):
     pass
 
@@ -183,6 +207,11 @@ SIGNATURES = {
     "sit_sac_target_args_size": (c_size_t, []),
     "sit_sac_target": (c_int32, [c_void_p, POINTER(SacTargetArgs), c_void_p]),
     "sit_sac_polyak": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p]),
+    "sit_sac_workspace_floats": (c_int64, [c_int32]),
+    "sit_sac_critic_step_args_size": (c_size_t, []),
+    "sit_sac_policy_step_args_size": (c_size_t, []),
+    "sit_sac_critic_step": (c_int32, [c_void_p, POINTER(SacCriticStepArgs), c_void_p]),
+    "sit_sac_policy_step": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
 }
 
 _lib = None
@@ -215,7 +244,9 @@ def load():
         raise ImportError(f"sit_episodes_args layout mismatch: C {lib.sit_episodes_args_size()} vs "
                           f"ctypes {ctypes.sizeof(EpisodesArgs)} bytes")
     for fn, struct in (("sit_replay_push_args_size", ReplayPushArgs), ("sit_replay_sample_args_size", ReplaySampleArgs),
-                       ("sit_sac_target_args_size", SacTargetArgs)):
+                       ("sit_sac_target_args_size", SacTargetArgs),
+                       ("sit_sac_critic_step_args_size", SacCriticStepArgs),
+                       ("sit_sac_policy_step_args_size", SacPolicyStepArgs)):
         if hasattr(lib, fn) and getattr(lib, fn)() != ctypes.sizeof(struct):
             raise ImportError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} vs ctypes {ctypes.sizeof(struct)} bytes")
     _lib = lib

@@ -8,6 +8,7 @@
 #include "sit_episodes.h"
 #include "sit_replay.h"
 #include "sit_sac.h"
+#include "sit_sac_grad.h"
 
 #ifdef SIT_F32_TU
 int sit_launch_steps_f32(sit_handle* h, const void* io, void* stream);   // sit_steps_f32.hip
@@ -752,6 +753,23 @@ int sit_sac_polyak(sit_handle* h, float* target, const float* online, int64_t n,
   if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
   if (const char* why = sac_polyak_args_error(target, online, n)) return fail(h, SIT_E_INVALID, "%s", why);
   return sac_launch_polyak(h, target, online, n, tau, (hipStream_t)stream);
+}
+
+// ---- SAC learner, the gradient half (sit_sac_grad.h) -----------------------------------------
+int64_t sit_sac_workspace_floats(int32_t batch) { return sac_workspace_floats(batch); }
+size_t sit_sac_critic_step_args_size(void) { return sizeof(sit_sac_critic_step_args); }
+size_t sit_sac_policy_step_args_size(void) { return sizeof(sit_sac_policy_step_args); }
+
+int sit_sac_critic_step(sit_handle* h, const sit_sac_critic_step_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_critic_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_critic_step<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+int sit_sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_policy_step<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -136,8 +136,8 @@ __device__ __forceinline__ void sac_mlp(const float* __restrict__ w, SacLds& S) 
 
 // standard normal of (seed, row, update): Philox4x32-10(key = seed, ctr = (row, 0x5441, update lo,
 // update hi)), then sampler_normal's Box-Muller step (sit_device.h)
-__device__ __forceinline__ double sac_normal(uint64_t seed, uint32_t row, uint64_t update) {
-  uint32_t c[4] = {row, kSacTag, (uint32_t)update, (uint32_t)(update >> 32)};
+__device__ __forceinline__ double sac_normal(uint64_t seed, uint32_t row, uint64_t update, uint32_t tag = kSacTag) {
+  uint32_t c[4] = {row, tag, (uint32_t)update, (uint32_t)(update >> 32)};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const double u1 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6) + 1.0) * (1.0 / 9007199254740992.0);
   const double u2 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6)) * (1.0 / 9007199254740992.0);
@@ -147,7 +147,8 @@ __device__ __forceinline__ double sac_normal(uint64_t seed, uint32_t row, uint64
 // log(1 - tanh(x)^2 + 1e-6) without the cancellation of 1 - a * a: with em = expm1(2|x|) (formed as
 // actor_tanh forms it), 1 - tanh(x)^2 = 4 (em + 1) / (em + 2)^2, every factor a positive number known to
 // a few ulp.  |x| is capped at 40 (em < 6e34 stays finite; the term is below 1e-68 there, against 1e-6).
-__device__ __forceinline__ float sac_log_one_minus_sq(float x) {
+// sac_one_minus_sq is 1 - tanh(x)^2 itself (the policy step's backward pass needs it too).
+__device__ __forceinline__ float sac_one_minus_sq(float x) {
 #pragma clang fp reassociate(off) contract(off)
   const float ax = __builtin_fminf(__builtin_fabsf(x), 40.0f);
   const float t = ax + ax;
@@ -166,8 +167,12 @@ __device__ __forceinline__ float sac_log_one_minus_sq(float x) {
     em = actor_exp(t) - 1.0f;
   }
   const float rc = 1.0f / (em + 2.0f);
-  const float s = (4.0f * ((em + 1.0f) * rc)) * rc;     // (em + 1) / (em + 2) <= 1: no overflow
-  return logf(s + 1e-6f);
+  return (4.0f * ((em + 1.0f) * rc)) * rc;              // (em + 1) / (em + 2) <= 1: no overflow
+}
+
+__device__ __forceinline__ float sac_log_one_minus_sq(float x) {
+#pragma clang fp reassociate(off) contract(off)
+  return logf(sac_one_minus_sq(x) + 1e-6f);
 }
 
 template <typename T>

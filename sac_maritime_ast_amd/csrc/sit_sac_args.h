@@ -1,6 +1,7 @@
-// sit_sac_args.h — argument checks of sit_sac_target / sit_sac_polyak (include/sit.h), host code that
-// depends on nothing but the public header: the library calls them before any launch, and
-// tests/csrc/sac_args_main.cpp calls them alone under ASan + UBSan.
+// sit_sac_args.h — argument checks of sit_sac_target / sit_sac_polyak and of sit_sac_critic_step /
+// sit_sac_policy_step (include/sit.h), host code that depends on nothing but the public header: the
+// library calls them before any launch, and tests/csrc/sac_args_main.cpp and
+// tests/csrc/sac_update_args_main.cpp call them alone under ASan + UBSan.
 //
 // Each returns NULL for acceptable arguments, or a static string naming the first thing wrong.
 #ifndef SIT_SAC_ARGS_H
@@ -38,6 +39,69 @@ inline const char* sac_polyak_args_error(const float* target, const float* onlin
   if ((uintptr_t)target % kSacWeightAlign) return "sac: target must be 16-byte aligned";
   if ((uintptr_t)online % kSacWeightAlign) return "sac: online must be 16-byte aligned";
   return nullptr;
+}
+
+// the float32 workspace of the gradient half: two network passes of SIT_SAC_WORKSPACE_ROW floats per row
+inline int64_t sac_workspace_floats(int32_t batch) {
+  return batch > 0 ? 2 * (int64_t)batch * SIT_SAC_WORKSPACE_ROW : 0;
+}
+
+inline const char* sac_adam_error(const sit_sac_adam* o) {
+  if (!(o->lr >= 0.0)) return "sac: lr must be >= 0";
+  if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0)) return "sac: betas must lie in [0, 1)";
+  if (!(o->eps >= 0.0)) return "sac: eps must be >= 0";
+  if (!(o->bias1 > 0.0 && o->bias1 <= 1.0) || !(o->bias2 > 0.0 && o->bias2 <= 1.0))
+    return "sac: the bias corrections must lie in (0, 1]";
+  return nullptr;
+}
+
+inline const char* sac_critic_step_args_error(const sit_sac_critic_step_args* a) {
+  if (!a) return "sac: null args";
+  if (a->batch <= 0) return "sac: batch must be positive";
+  if (!a->critic_weights) return "sac: critic_weights is required";
+  if (!a->critic_m) return "sac: critic_m is required";
+  if (!a->critic_v) return "sac: critic_v is required";
+  if (!a->state) return "sac: state is required";
+  if (!a->action) return "sac: action is required";
+  if (!a->y) return "sac: y is required";
+  if (!a->workspace) return "sac: workspace is required";
+  if (!a->results) return "sac: results is required";
+  if ((uintptr_t)a->critic_weights % kSacWeightAlign) return "sac: critic_weights must be 16-byte aligned";
+  if ((uintptr_t)a->critic_m % kSacWeightAlign) return "sac: critic_m must be 16-byte aligned";
+  if ((uintptr_t)a->critic_v % kSacWeightAlign) return "sac: critic_v must be 16-byte aligned";
+  if ((uintptr_t)a->workspace % sizeof(float)) return "sac: workspace must be 4-byte aligned";
+  if ((uintptr_t)a->results % sizeof(float)) return "sac: results must be 4-byte aligned";
+  if (a->workspace_floats < sac_workspace_floats(a->batch)) return "sac: workspace is too small";
+  return sac_adam_error(&a->adam);
+}
+
+inline const char* sac_policy_step_args_error(const sit_sac_policy_step_args* a) {
+  if (!a) return "sac: null args";
+  if (a->batch <= 0) return "sac: batch must be positive";
+  if (!a->actor_weights) return "sac: actor_weights is required";
+  if (!a->actor_m) return "sac: actor_m is required";
+  if (!a->actor_v) return "sac: actor_v is required";
+  if (!a->critic_weights) return "sac: critic_weights is required";
+  if (!a->alpha) return "sac: alpha is required";
+  if (a->tune && !a->log_alpha) return "sac: log_alpha is required";
+  if (a->tune && !a->log_alpha_m) return "sac: log_alpha_m is required";
+  if (a->tune && !a->log_alpha_v) return "sac: log_alpha_v is required";
+  if (!a->state) return "sac: state is required";
+  if (!a->workspace) return "sac: workspace is required";
+  if (!a->results) return "sac: results is required";
+  if ((uintptr_t)a->actor_weights % kSacWeightAlign) return "sac: actor_weights must be 16-byte aligned";
+  if ((uintptr_t)a->actor_m % kSacWeightAlign) return "sac: actor_m must be 16-byte aligned";
+  if ((uintptr_t)a->actor_v % kSacWeightAlign) return "sac: actor_v must be 16-byte aligned";
+  if ((uintptr_t)a->critic_weights % kSacWeightAlign) return "sac: critic_weights must be 16-byte aligned";
+  if ((uintptr_t)a->alpha % sizeof(float)) return "sac: alpha must be 4-byte aligned";
+  if (a->tune && ((uintptr_t)a->log_alpha % sizeof(float) || (uintptr_t)a->log_alpha_m % sizeof(float) ||
+                  (uintptr_t)a->log_alpha_v % sizeof(float)))
+    return "sac: log_alpha and its moments must be 4-byte aligned";
+  if ((uintptr_t)a->workspace % sizeof(float)) return "sac: workspace must be 4-byte aligned";
+  if ((uintptr_t)a->results % sizeof(float)) return "sac: results must be 4-byte aligned";
+  if (a->workspace_floats < sac_workspace_floats(a->batch)) return "sac: workspace is too small";
+  if (const char* why = sac_adam_error(&a->adam)) return why;
+  return a->tune ? sac_adam_error(&a->alpha_adam) : nullptr;
 }
 
 }  // namespace

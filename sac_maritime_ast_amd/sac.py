@@ -7,7 +7,10 @@ automatic entropy tuning, target_update_interval 1, batch_size 64 -- standard SA
 2018) with the actor of ``samplers.GaussianPolicy``.
 
 One update has two halves.  The gradient half (two critic losses, the policy loss, the temperature
-loss and their Adam steps) is PyTorch autograd.  The no-gradient half is inference only and is HIP
+loss and their Adam steps) is PyTorch autograd by default, or with ``SacLearner(gradient="hip")`` the
+HIP calls ``sit_sac_critic_step`` / ``sit_sac_policy_step`` (csrc/sit_sac_grad.h: forward and backward
+passes per row, weight gradients fused with Adam), which update the packed blocks in place; the
+networks' parameters are then views into those blocks.  The no-gradient half is inference only and is HIP
 (csrc/sit_sac.h, include/sit.h "SAC learner"): ``sit_sac_target`` evaluates the actor at next_state
 with its log-probability, both target critics at (next_state, a') and the TD target in one kernel, and
 ``sit_sac_polyak`` moves the packed target block towards the online critics in another.
@@ -17,7 +20,8 @@ architectures ``pack_actor_weights`` / ``pack_critic_weights`` decline).
 ``sac_target_reference`` is the executable specification of ``sit_sac_target`` in float64 NumPy,
 noise draw included; ``sac_update_reference`` is a whole update in float64 PyTorch on the CPU.
 
-Not included: HIP backward passes, graph capture of an update, prioritised replay, n-step returns,
+Not included: graph capture of an update, a device-side results queue (each update reads its five
+results on the host), HIP gradients for other architectures, prioritised replay, n-step returns,
 observation normalisation, multi-rank learners.
 """
 from __future__ import annotations
@@ -118,6 +122,76 @@ def unpack_critic_weights(block: torch.Tensor, q: nn.Module) -> nn.Module:
         for t, shape, o in _critic_segments(layers):
             t.copy_(flat[o:o + t.numel()].view(shape))
     return q
+
+
+def _actor_layers(policy: nn.Module):
+    """(l1, l2, l3) when policy is the reference's actor (``pack_actor_weights`` accepts it), else None."""
+    net = getattr(policy, "net", None)
+    if net is None or pack_actor_weights(policy) is None:
+        return None
+    return net[0], net[2], net[4]
+
+
+def block_views(block: torch.Tensor, layers) -> list:
+    """Views into a packed block (or a moment block of the same layout), one per parameter in
+    ``parameters()`` order and of the parameter's shape: `layers` is ``[(l1, l2, l3)]`` of the actor or
+    ``_critic_layers(q)`` of the twin critic.  l2.weight's view is the transpose of its W2^T segment."""
+    flat, out, o = block.view(-1), [], 0
+    stride = CRITIC_WEIGHTS if len(layers) == 2 else 0
+    for c, (l1, l2, l3) in enumerate(layers):
+        o = c * stride
+        for p, transposed in ((l1.weight, False), (l1.bias, False), (l2.weight, True), (l2.bias, False),
+                              (l3.weight, False), (l3.bias, False)):
+            n = p.numel()
+            seg = flat[o:o + n]
+            out.append(seg.view(p.shape[1], p.shape[0]).t() if transposed else seg.view(p.shape))
+            o += n
+    return out
+
+
+def bind_parameters(block: torch.Tensor, layers) -> list:
+    """Make the layers' parameters views into `block` (which must hold their values already:
+    ``pack_actor_weights`` / ``pack_critic_weights``).  The Parameter objects stay the same; an in-place
+    write to the block is a write to the module.  Returns the parameters, in ``parameters()`` order."""
+    params = [p for ls in layers for l in ls for p in (l.weight, l.bias)]
+    for p, v in zip(params, block_views(block, layers)):
+        p.data = v
+    return params
+
+
+def touch_parameters(params) -> None:
+    """Bump the version counters of parameters whose storage a kernel has written, so that change
+    detection by ``_version`` (``PolicySampler.launch``) sees the write."""
+    torch.autograd.graph.increment_version(list(params))
+
+
+def moments_to_adam_state(m: torch.Tensor, v: torch.Tensor, layers, step: int) -> dict:
+    """``torch.optim.Adam.state_dict()["state"]`` of packed moment blocks: per parameter index step,
+    exp_avg, exp_avg_sq (contiguous, the parameter's shape).  Empty before the first step, as torch's."""
+    if step <= 0:
+        return {}
+    return {i: {"step": torch.tensor(float(step)), "exp_avg": a.clone(memory_format=torch.contiguous_format),
+                "exp_avg_sq": b.clone(memory_format=torch.contiguous_format)}
+            for i, (a, b) in enumerate(zip(block_views(m, layers), block_views(v, layers)))}
+
+
+def adam_state_to_moments(state: dict, m: torch.Tensor, v: torch.Tensor, layers) -> int:
+    """The inverse: fill the packed moment blocks from an Adam state (zeros when it is empty) and return
+    the step count."""
+    with torch.no_grad():
+        m.zero_()
+        v.zero_()
+        if not state:
+            return 0
+        steps = set()
+        for i, (a, b) in enumerate(zip(block_views(m, layers), block_views(v, layers))):
+            st = state[i]
+            a.copy_(st["exp_avg"])
+            b.copy_(st["exp_avg_sq"])
+            steps.add(int(st["step"]))
+        if len(steps) != 1:
+            raise ValueError(f"adam_state_to_moments: parameters at different steps {sorted(steps)}")
+        return steps.pop()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -262,6 +336,14 @@ class SacLearner:
     only as the packed block ``target_weights``; it needs the reference's architectures
     (``pack_actor_weights`` / ``pack_critic_weights``) and raises for others -- pick target="torch" for
     those, which computes the same formulas with PyTorch ops on a target ``QNetwork``.
+    gradient="torch" (the default): the gradient half is autograd and three ``torch.optim.Adam``.
+    gradient="hip": it is ``sit_sac_critic_step`` / ``sit_sac_policy_step``; it needs target="hip" and the
+    reference's architectures.  The packed blocks ``actor_weights`` and ``online_weights`` are then the
+    master copy of the parameters, the Adam moments are packed blocks of the same layout, and the
+    parameters of `policy` and ``critic`` are views into the blocks (``bind_parameters``), so both modules
+    hold the current values after every update without a copy.  The policy noise is drawn on the device
+    from (seed, update) (``policy_noise`` is its specification).  A checkpoint of either mode loads into
+    the other.
 
     ``actor_weights`` is the packed actor block sit_sac_target reads, repacked in place at the end of
     every update.  A ``PolicySampler`` built on the same `policy` keeps a block of its own: call its
@@ -270,10 +352,16 @@ class SacLearner:
 
     def __init__(self, env, policy: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
                  alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
-                 reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None):
+                 reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None,
+                 gradient: str = "torch"):
         if target not in ("hip", "torch"):
             raise ValueError("target must be 'hip' or 'torch'")
-        self.env, self.policy, self.target = env, policy, target
+        if gradient not in ("hip", "torch"):
+            raise ValueError("gradient must be 'hip' or 'torch'")
+        if gradient == "hip" and target != "hip":
+            raise ValueError("gradient='hip' needs target='hip'")
+        self.env, self.policy, self.target, self.gradient = env, policy, target, gradient
+        self.lr, self.target_entropy = float(lr), -1.0
         self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
         self.target_update_interval, self.seed = int(target_update_interval), int(seed)
         self.auto = bool(automatic_entropy_tuning)
@@ -301,6 +389,17 @@ class SacLearner:
             self.actor_weights = pack_actor_weights(policy)      # None for other architectures
             self.online_weights = self.target_weights = None
             self.target_critic = copy.deepcopy(self.critic).requires_grad_(False)
+        if gradient == "hip":
+            self._layers = {"policy": [_actor_layers(self.policy)], "critic": _critic_layers(self.critic)}
+            self._blocks = {"policy": self.actor_weights, "critic": self.online_weights}
+            self._params = (bind_parameters(self.actor_weights, self._layers["policy"])
+                            + bind_parameters(self.online_weights, self._layers["critic"]))
+            self._m = {k: torch.zeros_like(b) for k, b in self._blocks.items()}
+            self._v = {k: torch.zeros_like(b) for k, b in self._blocks.items()}
+            self._m["alpha"], self._v["alpha"] = torch.zeros_like(self.alpha), torch.zeros_like(self.alpha)
+            self._steps = {k: 0 for k in self.optims}
+            self._results = torch.zeros(5, dtype=torch.float32, device=dev)
+            self._ws = None
 
     # ---------------- the no-gradient half ----------------
     def td_target(self, next_state, reward, mask, update: int, noise=None, diagnostics: dict | None = None):
@@ -356,6 +455,8 @@ class SacLearner:
                 return None
             self._ready = True        # a ring never shrinks
         raw = _sample(memory, B)
+        if self.gradient == "hip":
+            return self._hip_update(raw, B, updates)
         if self.target == "hip":
             y = self.td_target(raw["next_state"], raw["reward"], raw["mask"], updates).to(torch.float32)
             batch = {k: v.to(torch.float32) for k, v in raw.items()}
@@ -375,15 +476,101 @@ class SacLearner:
             pack_actor_weights(self.policy, out=self.actor_weights)
         return tuple(torch.stack([l1, l2, lp, la.reshape(()), self.alpha[0]]).tolist())
 
+    # ---------------- one update, gradient="hip" ----------------
+    def _adam(self, key: str) -> _lib.SacAdam:
+        """The scalars of one Adam step of optimiser `key`; its step count advances here, on the host."""
+        self._steps[key] += 1
+        t = self._steps[key]
+        g = self.optims[key].param_groups[0]
+        b1, b2 = g["betas"]
+        return _lib.SacAdam(float(g["lr"]), float(b1), float(b2), float(g["eps"]), 1.0 - b1 ** t, 1.0 - b2 ** t)
+
+    def _hip_update(self, raw, B: int, updates: int):
+        dt, dev = self.env.dtype, self.env.device
+        y = self.td_target(raw["next_state"], raw["reward"], raw["mask"], updates)
+        state, action = raw["state"], raw["action"]
+        for name, t in (("state", state), ("action", action)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous {dt} tensor on {dev} is required")
+        n_ws = 2 * B * _lib.SIT_SAC_WORKSPACE_ROW
+        if self._ws is None or self._ws.numel() < n_ws:
+            self._ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        c = _lib.SacCriticStepArgs()
+        c.batch, c.workspace_floats, c.adam = B, self._ws.numel(), self._adam("critic")
+        c.critic_weights, c.critic_m, c.critic_v = (self.online_weights.data_ptr(), self._m["critic"].data_ptr(),
+                                                    self._v["critic"].data_ptr())
+        c.state, c.action, c.y = state.data_ptr(), action.data_ptr(), y.data_ptr()
+        c.workspace, c.results = self._ws.data_ptr(), self._results.data_ptr()
+        p = _lib.SacPolicyStepArgs()
+        p.batch, p.tune, p.workspace_floats = B, int(self.auto), self._ws.numel()
+        p.seed, p.update = self.seed & 0xFFFFFFFFFFFFFFFF, int(updates) & 0xFFFFFFFFFFFFFFFF
+        p.target_entropy, p.adam = self.target_entropy, self._adam("policy")
+        p.actor_weights, p.actor_m, p.actor_v = (self.actor_weights.data_ptr(), self._m["policy"].data_ptr(),
+                                                 self._v["policy"].data_ptr())
+        p.critic_weights, p.alpha = self.online_weights.data_ptr(), self.alpha.data_ptr()
+        if self.auto:
+            p.alpha_adam = self._adam("alpha")
+            p.log_alpha, p.log_alpha_m, p.log_alpha_v = (self.log_alpha.data_ptr(), self._m["alpha"].data_ptr(),
+                                                         self._v["alpha"].data_ptr())
+        p.state, p.noise = state.data_ptr(), None
+        p.workspace, p.results = self._ws.data_ptr(), self._results.data_ptr()
+        with torch.cuda.device(dev):
+            stream = self.env._stream()
+            self.env._call("sit_sac_critic_step", byref(c), stream)
+            self.env._call("sit_sac_policy_step", byref(p), stream)
+            if updates % self.target_update_interval == 0:
+                self.env._call("sit_sac_polyak", c_void_p(self.target_weights.data_ptr()),
+                               c_void_p(self.online_weights.data_ptr()), self.online_weights.numel(), self.tau, stream)
+        touch_parameters(self._params + ([self.log_alpha] if self.auto else []))
+        return tuple(self._results.tolist())
+
+    def _optim_state_dicts(self) -> dict:
+        """The three optimisers' state in ``torch.optim.Adam.state_dict()`` form (both gradient modes write
+        this one format; in hip mode the moments come from the packed blocks and the host's step counts)."""
+        if self.gradient != "hip":
+            return {k: copy.deepcopy(o.state_dict()) for k, o in self.optims.items()}
+        out = {}
+        for k, o in self.optims.items():
+            sd = copy.deepcopy(o.state_dict())
+            if k == "alpha":
+                sd["state"] = {} if self._steps[k] <= 0 else {0: {"step": torch.tensor(float(self._steps[k])),
+                                                                  "exp_avg": self._m[k].clone(),
+                                                                  "exp_avg_sq": self._v[k].clone()}}
+            else:
+                sd["state"] = moments_to_adam_state(self._m[k], self._v[k], self._layers[k], self._steps[k])
+            out[k] = sd
+        return out
+
+    def _load_optim_state_dicts(self, optims: dict):
+        if self.gradient != "hip":
+            for k, o in self.optims.items():
+                o.load_state_dict(optims[k])
+            return
+        for k, o in self.optims.items():
+            o.load_state_dict({"state": {}, "param_groups": optims[k]["param_groups"]})    # lr, betas, eps
+            state = optims[k]["state"]
+            if k == "alpha":
+                with torch.no_grad():
+                    self._m[k].zero_()
+                    self._v[k].zero_()
+                    if state:
+                        self._m[k].copy_(state[0]["exp_avg"])
+                        self._v[k].copy_(state[0]["exp_avg_sq"])
+                self._steps[k] = int(state[0]["step"]) if state else 0
+            else:
+                self._steps[k] = adam_state_to_moments(state, self._m[k], self._v[k], self._layers[k])
+
     # ---------------- checkpoint ----------------
     def state_dict(self) -> dict:
-        """Networks, optimisers, targets (as the packed block, in both modes) and log_alpha."""
+        """Networks, optimisers (in ``torch.optim.Adam``'s form in both gradient modes: in hip mode the packed
+        moment blocks and the step counts, converted), targets (as the packed block, in both modes) and
+        log_alpha."""
         tw = self.target_weights if self.target == "hip" else pack_critic_weights(self.target_critic)
         return {"policy": copy.deepcopy(self.policy.state_dict()), "critic": copy.deepcopy(self.critic.state_dict()),
                 "critic_target": None if tw is None else tw.clone(),
                 "critic_target_state": None if tw is not None else copy.deepcopy(self.target_critic.state_dict()),
                 "log_alpha": self.log_alpha.detach().clone(),
-                "optims": {k: copy.deepcopy(o.state_dict()) for k, o in self.optims.items()}}
+                "optims": self._optim_state_dicts()}
 
     def load_state_dict(self, sd: dict):
         self.policy.load_state_dict(sd["policy"])
@@ -392,7 +579,8 @@ class SacLearner:
             if sd.get("critic_target") is None:
                 raise ValueError("this checkpoint holds no packed target block")
             self.target_weights.copy_(sd["critic_target"])
-            pack_critic_weights(self.critic, out=self.online_weights)
+            if self.gradient != "hip":                   # there the parameters are the block
+                pack_critic_weights(self.critic, out=self.online_weights)
         elif sd.get("critic_target") is not None:
             unpack_critic_weights(sd["critic_target"].to(self.env.device), self.target_critic)
         else:
@@ -400,9 +588,10 @@ class SacLearner:
         with torch.no_grad():
             self.log_alpha.copy_(sd["log_alpha"])
             self.alpha.copy_(self.log_alpha.detach().exp())
-        for k, o in self.optims.items():
-            o.load_state_dict(sd["optims"][k])
-        if self.actor_weights is not None:
+        self._load_optim_state_dicts(sd["optims"])
+        if self.gradient == "hip":
+            touch_parameters(self._params)
+        elif self.actor_weights is not None:
             pack_actor_weights(self.policy, out=self.actor_weights)
 
 
@@ -454,5 +643,6 @@ def sac_update_reference(policy: nn.Module, critic: nn.Module, **kw) -> SacUpdat
 
 
 __all__ = ["QNetwork", "SacLearner", "SacUpdateReference", "pack_critic_weights",
-           "unpack_critic_weights", "sac_noise", "policy_noise", "log_one_minus_tanh_sq", "sac_target_reference", "torch_target",
+           "unpack_critic_weights", "block_views", "bind_parameters", "touch_parameters", "moments_to_adam_state",
+           "adam_state_to_moments", "sac_noise", "policy_noise", "log_one_minus_tanh_sq", "sac_target_reference", "torch_target",
            "sac_update_reference"]

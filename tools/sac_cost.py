@@ -2,6 +2,7 @@
 """Cost of the SAC learner's no-gradient half: the fused HIP path next to PyTorch (GPU).
 
     python3 tools/sac_cost.py [--calls 30] [--warmup 5] [out.json]
+    python3 tools/sac_cost.py --gradient [--calls 30] [--warmup 5] [out.json]
 
 float32 handle of 64 envs, the reference's networks (actor 10-256-256-2, twin critic 11-256-256-1,
 default initialisation), a ring of 4096 synthetic normalised records.  Every figure is the median of
@@ -15,7 +16,15 @@ default initialisation), a ring of 4096 synthetic normalised records.  Every fig
            ends with the host reading the five results, so the span is also the wall time)
 
 and the share of an update the no-gradient half takes (target + Polyak over the update).  There is no
-pass threshold; the result goes to profiles/r08_sac_cost.json."""
+pass threshold; the result goes to profiles/r08_sac_cost.json.
+
+--gradient measures the gradient half instead (profiles/r09_sac_update_cost.json), the same way:
+
+  update   a whole SacLearner.update_parameters at batch 64 with gradient="hip" and gradient="torch" (both
+           target="hip"), interleaved call by call
+  calls    sit_sac_critic_step and sit_sac_policy_step alone, on a learner's own blocks
+  read     the host read of the five results alone (``_results.tolist()`` on an idle stream), and its share
+           of a gradient="hip" update"""
 import argparse
 import copy
 import json
@@ -32,8 +41,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "r08_sac_cost.json"))
+    ap.add_argument("--gradient", action="store_true", help="measure the gradient half (r09_sac_update_cost.json)")
+    ap.add_argument("out", nargs="?", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r09_sac_update_cost.json" if a.gradient else "r08_sac_cost.json")
     if a.calls < 20:
         ap.error("time at least 20 calls")
     import torch
@@ -47,8 +59,9 @@ def main():
     torch.manual_seed(0)
     pol0, q0 = GaussianPolicy(), sac.QNetwork()
 
-    def learner(target):
-        return sac.SacLearner(env, copy.deepcopy(pol0).to(dev), critic=copy.deepcopy(q0), target=target, seed=1)
+    def learner(target, gradient="torch"):
+        return sac.SacLearner(env, copy.deepcopy(pol0).to(dev), critic=copy.deepcopy(q0), target=target, seed=1,
+                              gradient=gradient)
 
     def memory():
         mem = ReplayMemory(env, 4096, seed=1)
@@ -59,7 +72,6 @@ def main():
         mem.cursor[0] = 4096
         return mem
 
-    hip, tor = learner("hip"), learner("torch")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
 
     def span(fn):
@@ -79,6 +91,16 @@ def main():
                     t[k].append(us)
         return {k: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for k, v in t.items()}
 
+    def finish(res):
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        env.close()
+
+    if a.gradient:
+        return finish(gradient_half(a, torch, env, _lib, learner, memory, interleaved))
+    hip, tor = learner("hip"), learner("torch")
     res = {"what": __doc__.split("\n\n")[0], "calls": a.calls, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0), "target": {}, "polyak": {}, "update": {}}
     # ---- target ----
@@ -123,11 +145,69 @@ def main():
         "hip": (t64["hip"]["median_us"] + res["polyak"]["hip_repack_and_kernel"]["median_us"]) / r["hip"]["median_us"],
         "torch": (t64["torch"]["median_us"] + res["polyak"]["torch"]["median_us"]) / r["torch"]["median_us"]}
     res["faster_update_at_batch_64"] = "hip" if r["hip"]["median_us"] <= r["torch"]["median_us"] else "torch"
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps(res))
-    env.close()
+    finish(res)
+
+
+def gradient_half(a, torch, env, _lib, learner, memory, interleaved):
+    """The --gradient measurement (see the module docstring)."""
+    from ctypes import byref
+    B = 64
+    lrn = {"hip": learner("hip", "hip"), "torch": learner("hip", "torch")}
+    mems = {k: memory() for k in lrn}
+    count = {k: 0 for k in lrn}
+    wall = {k: [] for k in lrn}
+
+    def update(mode):
+        def fn():
+            t0 = time.perf_counter()
+            out = lrn[mode].update_parameters(mems[mode], B, count[mode])
+            wall[mode].append((time.perf_counter() - t0) * 1e6)
+            count[mode] += 1
+            assert out is not None
+        return fn
+    res = {"what": "Cost of a SAC update with the gradient half in HIP (gradient='hip') next to autograd "
+                   "(gradient='torch'), batch 64 (GPU).", "calls": a.calls, "warmup": a.warmup,
+           "device": torch.cuda.get_device_name(0), "parent_update_us": 3411.4, "parent_source": "profiles/r08_sac_cost.json"}
+    r = interleaved({k: update(k) for k in lrn})
+    for mode in lrn:
+        r[mode]["wall_median_us"] = statistics.median(wall[mode][a.warmup:])
+    r["torch_over_hip"] = r["torch"]["median_us"] / r["hip"]["median_us"]
+    res["update"] = r
+    # ---- the two calls alone, on a third learner's blocks (its parameters move as in training) ----
+    h = learner("hip", "hip")
+    dev, dt = env.device, env.dtype
+    state, action, y = (torch.randn(B, 10, device=dev, dtype=dt), torch.rand(B, device=dev, dtype=dt) * 2 - 1,
+                        torch.randn(B, device=dev, dtype=dt))
+    ws = torch.empty(2 * B * _lib.SIT_SAC_WORKSPACE_ROW, dtype=torch.float32, device=dev)
+    c, p = _lib.SacCriticStepArgs(), _lib.SacPolicyStepArgs()
+    c.batch, c.workspace_floats = B, ws.numel()
+    c.critic_weights, c.critic_m, c.critic_v = h.online_weights.data_ptr(), h._m["critic"].data_ptr(), h._v["critic"].data_ptr()
+    c.state, c.action, c.y, c.workspace, c.results = (state.data_ptr(), action.data_ptr(), y.data_ptr(), ws.data_ptr(),
+                                                      h._results.data_ptr())
+    p.batch, p.tune, p.workspace_floats, p.seed, p.target_entropy = B, 1, ws.numel(), 1, -1.0
+    p.actor_weights, p.actor_m, p.actor_v = h.actor_weights.data_ptr(), h._m["policy"].data_ptr(), h._v["policy"].data_ptr()
+    p.critic_weights, p.alpha = h.online_weights.data_ptr(), h.alpha.data_ptr()
+    p.log_alpha, p.log_alpha_m, p.log_alpha_v = h.log_alpha.data_ptr(), h._m["alpha"].data_ptr(), h._v["alpha"].data_ptr()
+    p.state, p.workspace, p.results = state.data_ptr(), ws.data_ptr(), h._results.data_ptr()
+    n = {"u": 0}
+
+    def critic_step():
+        c.adam = h._adam("critic")
+        with torch.cuda.device(dev):
+            env._call("sit_sac_critic_step", byref(c), env._stream())
+
+    def policy_step():
+        n["u"] += 1
+        p.update, p.adam, p.alpha_adam = n["u"], h._adam("policy"), h._adam("alpha")
+        with torch.cuda.device(dev):
+            env._call("sit_sac_policy_step", byref(p), env._stream())
+    res["calls_alone"] = interleaved({"sit_sac_critic_step": critic_step, "sit_sac_policy_step": policy_step,
+                                      "results_host_read": lambda: h._results.tolist()})
+    assert all(v == v for v in h._results.tolist())
+    res["host_read_share_of_hip_update"] = res["calls_alone"]["results_host_read"]["median_us"] / r["hip"]["median_us"]
+    res["hip_update_over_parent"] = r["hip"]["median_us"] / res["parent_update_us"]
+    res["faster_update_at_batch_64"] = "hip" if r["hip"]["median_us"] <= r["torch"]["median_us"] else "torch"
+    return res
 
 
 if __name__ == "__main__":
