@@ -681,7 +681,15 @@ int sit_sac_polyak(sit_handle* h, float* target, const float* online, int64_t n,
  *
  * Workspace: float32, sit_sac_workspace_floats(batch) = 2 * batch * SIT_SAC_WORKSPACE_ROW elements, where
  * the row kernels leave each row's input, h1, h2, d1, d2, output gradients and loss terms for the Adam
- * kernels.  The two calls may share one workspace. */
+ * kernels.  The two calls may share one workspace.
+ *
+ * sit_sac_critic_step_tiled and sit_sac_policy_step_tiled take the same arguments, apply the same checks,
+ * need the same workspace and produce the same results as the plain calls, bit for bit: after the same row
+ * kernel they form each 32 x 32 tile of a weight gradient with the float32-input MFMA
+ * (v_mfma_f32_32x32x2_f32) instead of one serial sum per element.  The bits agree because the batch is the
+ * MFMA's k index: the instruction is a k-ordered float32 fmaf chain with one rounding per product, taken
+ * over the rows ascending from zero and never split, which is the sum above.  They are the calls for large
+ * batches, where the serial sum's time grows with B per element. */
 #define SIT_SAC_WORKSPACE_ROW 1040
 typedef struct sit_sac_adam {
   double lr, beta1, beta2, eps;
@@ -728,6 +736,8 @@ size_t sit_sac_critic_step_args_size(void);
 size_t sit_sac_policy_step_args_size(void);
 int sit_sac_critic_step(sit_handle* h, const sit_sac_critic_step_args* a, void* stream);
 int sit_sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
+int sit_sac_critic_step_tiled(sit_handle* h, const sit_sac_critic_step_args* a, void* stream);
+int sit_sac_policy_step_tiled(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
 
 #ifdef __cplusplus
 }

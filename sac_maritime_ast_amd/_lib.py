@@ -212,6 +212,8 @@ SIGNATURES = {
     "sit_sac_policy_step_args_size": (c_size_t, []),
     "sit_sac_critic_step": (c_int32, [c_void_p, POINTER(SacCriticStepArgs), c_void_p]),
     "sit_sac_policy_step": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
+    "sit_sac_critic_step_tiled": (c_int32, [c_void_p, POINTER(SacCriticStepArgs), c_void_p]),
+    "sit_sac_policy_step_tiled": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 #include "sit_replay.h"
 #include "sit_sac.h"
 #include "sit_sac_grad.h"
+#include "sit_sac_wgrad.h"
 
 #ifdef SIT_F32_TU
 int sit_launch_steps_f32(sit_handle* h, const void* io, void* stream);   // sit_steps_f32.hip
@@ -770,6 +771,19 @@ int sit_sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, void* 
   if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
   if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
   return with_real(h, [&](auto t) { return sac_launch_policy_step<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+// the same two calls with the weight gradients as MFMA tiles (sit_sac_wgrad.h)
+int sit_sac_critic_step_tiled(sit_handle* h, const sit_sac_critic_step_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_critic_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_critic_step_tiled<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+int sit_sac_policy_step_tiled(sit_handle* h, const sit_sac_policy_step_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_policy_step_tiled<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

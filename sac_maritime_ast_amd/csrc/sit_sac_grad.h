@@ -363,9 +363,10 @@ inline SacAdamScalars sac_adam_scalars(const sit_sac_adam& o) {
   return s;
 }
 
+// The two halves of each call, apart: the row kernel's launch and the arguments of the Adam kernel that
+// follows it (k_sac_adam here, k_sac_wgrad_adam of sit_sac_wgrad.h in the _tiled calls).
 template <typename T>
-int sac_launch_critic_step(sit_handle* h, const sit_sac_critic_step_args* s, hipStream_t stream) {
-  constexpr int kElems = 2 * SIT_CRITIC_WEIGHTS;
+int sac_launch_critic_fb(sit_handle* h, const sit_sac_critic_step_args* s, hipStream_t stream) {
   SacCriticFb<T> f{};
   f.batch = s->batch;
   f.critic = s->critic_weights;
@@ -375,12 +376,24 @@ int sac_launch_critic_step(sit_handle* h, const sit_sac_critic_step_args* s, hip
   f.ws = s->workspace;
   hipLaunchKernelGGL(k_sac_critic_fb<T>, dim3((unsigned)((s->batch + kSacRows - 1) / kSacRows)), dim3(256), 0, stream, f);
   HIP_TRY(h, hipGetLastError());
+  return SIT_OK;
+}
+
+inline SacAdam sac_critic_adam_args(const sit_sac_critic_step_args* s) {
   SacAdam a{};
   a.batch = s->batch;
   a.p = s->critic_weights; a.m = s->critic_m; a.v = s->critic_v;
   a.ws = s->workspace;
   a.results = s->results;
   a.o = sac_adam_scalars(s->adam);
+  return a;
+}
+
+template <typename T>
+int sac_launch_critic_step(sit_handle* h, const sit_sac_critic_step_args* s, hipStream_t stream) {
+  constexpr int kElems = 2 * SIT_CRITIC_WEIGHTS;
+  if (const int rc = sac_launch_critic_fb<T>(h, s, stream)) return rc;
+  const SacAdam a = sac_critic_adam_args(s);
   hipLaunchKernelGGL((k_sac_adam<kSacIn, 1, 2, SIT_CRITIC_WEIGHTS, false>), dim3((kElems + 255) / 256 + 1), dim3(256), 0,
                      stream, a);
   HIP_TRY(h, hipGetLastError());
@@ -388,7 +401,7 @@ int sac_launch_critic_step(sit_handle* h, const sit_sac_critic_step_args* s, hip
 }
 
 template <typename T>
-int sac_launch_policy_step(sit_handle* h, const sit_sac_policy_step_args* s, hipStream_t stream) {
+int sac_launch_policy_fb(sit_handle* h, const sit_sac_policy_step_args* s, hipStream_t stream) {
   SacPolicyFb<T> f{};
   f.batch = s->batch;
   f.seed = s->seed;
@@ -401,6 +414,10 @@ int sac_launch_policy_step(sit_handle* h, const sit_sac_policy_step_args* s, hip
   f.ws = s->workspace;
   hipLaunchKernelGGL(k_sac_policy_fb<T>, dim3((unsigned)((s->batch + kSacRows - 1) / kSacRows)), dim3(256), 0, stream, f);
   HIP_TRY(h, hipGetLastError());
+  return SIT_OK;
+}
+
+inline SacAdam sac_policy_adam_args(const sit_sac_policy_step_args* s) {
   SacAdam a{};
   a.batch = s->batch;
   a.p = s->actor_weights; a.m = s->actor_m; a.v = s->actor_v;
@@ -414,6 +431,13 @@ int sac_launch_policy_step(sit_handle* h, const sit_sac_policy_step_args* s, hip
     a.log_alpha = s->log_alpha; a.log_alpha_m = s->log_alpha_m; a.log_alpha_v = s->log_alpha_v;
     a.oa = sac_adam_scalars(s->alpha_adam);
   }
+  return a;
+}
+
+template <typename T>
+int sac_launch_policy_step(sit_handle* h, const sit_sac_policy_step_args* s, hipStream_t stream) {
+  if (const int rc = sac_launch_policy_fb<T>(h, s, stream)) return rc;
+  const SacAdam a = sac_policy_adam_args(s);
   hipLaunchKernelGGL((k_sac_adam<kActorObs, 2, 1, SIT_ACTOR_WEIGHTS, true>), dim3((SIT_ACTOR_WEIGHTS + 255) / 256 + 1),
                      dim3(256), 0, stream, a);
   HIP_TRY(h, hipGetLastError());

@@ -10,7 +10,10 @@ One update has two halves.  The gradient half (two critic losses, the policy los
 loss and their Adam steps) is PyTorch autograd by default, or with ``SacLearner(gradient="hip")`` the
 HIP calls ``sit_sac_critic_step`` / ``sit_sac_policy_step`` (csrc/sit_sac_grad.h: forward and backward
 passes per row, weight gradients fused with Adam), which update the packed blocks in place; the
-networks' parameters are then views into those blocks.  The no-gradient half is inference only and is HIP
+networks' parameters are then views into those blocks.  ``weight_gradient="mfma"`` swaps both for their
+``_tiled`` forms (csrc/sit_sac_wgrad.h), which form the weight gradients as 32 x 32 MFMA tiles over the
+batch instead of one serial sum per element: the same bits, and the choice for batches in the thousands.
+The no-gradient half is inference only and is HIP
 (csrc/sit_sac.h, include/sit.h "SAC learner"): ``sit_sac_target`` evaluates the actor at next_state
 with its log-probability, both target critics at (next_state, a') and the TD target in one kernel, and
 ``sit_sac_polyak`` moves the packed target block towards the online critics in another.
@@ -344,6 +347,10 @@ class SacLearner:
     hold the current values after every update without a copy.  The policy noise is drawn on the device
     from (seed, update) (``policy_noise`` is its specification).  A checkpoint of either mode loads into
     the other.
+    weight_gradient="sum" (the default): the plain calls, whose Adam kernel sums each element's gradient
+    over the rows in one thread.  weight_gradient="mfma": ``sit_sac_critic_step_tiled`` /
+    ``sit_sac_policy_step_tiled``, the same sums as MFMA tiles with the batch as the k index; it needs
+    gradient="hip", gives the same bits and keeps the same state, so checkpoints do not see it.
 
     ``actor_weights`` is the packed actor block sit_sac_target reads, repacked in place at the end of
     every update.  A ``PolicySampler`` built on the same `policy` keeps a block of its own: call its
@@ -353,13 +360,18 @@ class SacLearner:
     def __init__(self, env, policy: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
                  alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
                  reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None,
-                 gradient: str = "torch"):
+                 gradient: str = "torch", weight_gradient: str = "sum"):
         if target not in ("hip", "torch"):
             raise ValueError("target must be 'hip' or 'torch'")
         if gradient not in ("hip", "torch"):
             raise ValueError("gradient must be 'hip' or 'torch'")
         if gradient == "hip" and target != "hip":
             raise ValueError("gradient='hip' needs target='hip'")
+        if weight_gradient not in ("sum", "mfma"):
+            raise ValueError("weight_gradient must be 'sum' or 'mfma'")
+        if weight_gradient == "mfma" and gradient != "hip":
+            raise ValueError("weight_gradient='mfma' needs gradient='hip'")
+        self.weight_gradient = weight_gradient
         self.env, self.policy, self.target, self.gradient = env, policy, target, gradient
         self.lr, self.target_entropy = float(lr), -1.0
         self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
@@ -516,8 +528,9 @@ class SacLearner:
         p.workspace, p.results = self._ws.data_ptr(), self._results.data_ptr()
         with torch.cuda.device(dev):
             stream = self.env._stream()
-            self.env._call("sit_sac_critic_step", byref(c), stream)
-            self.env._call("sit_sac_policy_step", byref(p), stream)
+            tiled = "_tiled" if self.weight_gradient == "mfma" else ""
+            self.env._call("sit_sac_critic_step" + tiled, byref(c), stream)
+            self.env._call("sit_sac_policy_step" + tiled, byref(p), stream)
             if updates % self.target_update_interval == 0:
                 self.env._call("sit_sac_polyak", c_void_p(self.target_weights.data_ptr()),
                                c_void_p(self.online_weights.data_ptr()), self.online_weights.numel(), self.tau, stream)

@@ -2,10 +2,11 @@
 metadata notes (no GPU needed): every offload bundle in the library's .hip_fatbin section is unbundled
 (offload-bundle header parsed directly) and its AMDGPU metadata read with llvm-readelf --notes.
 
-    python tools/kernel_resources.py [lib.so] [name-filter]
+    python tools/kernel_resources.py [lib.so] [name-filter] [--json out.json]
 """
 from __future__ import annotations
 
+import json
 import os
 import re
 import struct
@@ -65,9 +66,15 @@ def kernels(lib: str) -> list[dict]:
 
 
 def main():
+    out = None
+    if "--json" in sys.argv:
+        at = sys.argv.index("--json")
+        out = sys.argv[at + 1]
+        del sys.argv[at:at + 2]
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(
         os.path.abspath(__file__))), "sac_maritime_ast_amd", "libsit.so")
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
+    rows = {}
     for k in kernels(lib):
         name = subprocess.run(["c++filt"], input=k["name"], capture_output=True, text=True).stdout.strip()
         if flt and flt not in name:
@@ -75,6 +82,15 @@ def main():
         print(f"{k.get('vgpr_count'):>4} vgpr {k.get('agpr_count'):>3} agpr {k.get('sgpr_count'):>4} sgpr "
               f"spill v{k.get('vgpr_spill_count')} s{k.get('sgpr_spill_count')} "
               f"lds {k.get('group_segment_fixed_size'):>6} scratch {k.get('private_segment_fixed_size'):>4}  {name[:150]}")
+        rows[name] = {"vgprs": int(k.get("vgpr_count")), "agprs": int(k.get("agpr_count")), "sgprs": int(k.get("sgpr_count")),
+                      "vgpr_spill": int(k.get("vgpr_spill_count")), "sgpr_spill": int(k.get("sgpr_spill_count")),
+                      "lds_bytes": int(k.get("group_segment_fixed_size")),
+                      "scratch_bytes_per_lane": int(k.get("private_segment_fixed_size")),
+                      "max_workgroup_size": int(k.get("max_flat_workgroup_size"))}
+    if out:
+        with open(out, "w") as f:
+            json.dump({"what": "tools/kernel_resources.py rows (code-object metadata notes), release flags",
+                       "library": os.path.basename(lib), "filter": flt, "arch": "gfx950", "kernels": rows}, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@
 
     python3 tools/sac_cost.py [--calls 30] [--warmup 5] [out.json]
     python3 tools/sac_cost.py --gradient [--calls 30] [--warmup 5] [out.json]
+    python3 tools/sac_cost.py --weight-gradient [--calls 30] [--warmup 5] [out.json]
 
 float32 handle of 64 envs, the reference's networks (actor 10-256-256-2, twin critic 11-256-256-1,
 default initialisation), a ring of 4096 synthetic normalised records.  Every figure is the median of
@@ -24,7 +25,16 @@ pass threshold; the result goes to profiles/r08_sac_cost.json.
            target="hip"), interleaved call by call
   calls    sit_sac_critic_step and sit_sac_policy_step alone, on a learner's own blocks
   read     the host read of the five results alone (``_results.tolist()`` on an idle stream), and its share
-           of a gradient="hip" update"""
+           of a gradient="hip" update
+
+--weight-gradient measures the tiled weight-gradient calls next to the plain ones
+(profiles/r10_sac_wgrad_cost.json), at B = 64, 256, 1024, 4096 and 16384 from a ring of 32768 records:
+
+  calls    sit_sac_critic_step against sit_sac_critic_step_tiled and sit_sac_policy_step against
+           sit_sac_policy_step_tiled, on a learner's own blocks, interleaved call by call
+  update   a whole SacLearner.update_parameters with weight_gradient="sum" and "mfma" (both gradient="hip")
+
+with, per pair, whether the tiled call's min-max range lies wholly below the plain call's."""
 import argparse
 import copy
 import json
@@ -42,10 +52,15 @@ def main():
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--gradient", action="store_true", help="measure the gradient half (r09_sac_update_cost.json)")
+    ap.add_argument("--weight-gradient", action="store_true",
+                    help="measure the tiled weight-gradient calls against the plain ones (r10_sac_wgrad_cost.json)")
     ap.add_argument("out", nargs="?", default=None)
     a = ap.parse_args()
+    if a.gradient and a.weight_gradient:
+        ap.error("--gradient and --weight-gradient are separate measurements")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r09_sac_update_cost.json" if a.gradient else "r08_sac_cost.json")
+        a.out = os.path.join(ROOT, "profiles", "r10_sac_wgrad_cost.json" if a.weight_gradient else
+                             "r09_sac_update_cost.json" if a.gradient else "r08_sac_cost.json")
     if a.calls < 20:
         ap.error("time at least 20 calls")
     import torch
@@ -59,17 +74,17 @@ def main():
     torch.manual_seed(0)
     pol0, q0 = GaussianPolicy(), sac.QNetwork()
 
-    def learner(target, gradient="torch"):
+    def learner(target, gradient="torch", weight_gradient="sum"):
         return sac.SacLearner(env, copy.deepcopy(pol0).to(dev), critic=copy.deepcopy(q0), target=target, seed=1,
-                              gradient=gradient)
+                              gradient=gradient, weight_gradient=weight_gradient)
 
-    def memory():
-        mem = ReplayMemory(env, 4096, seed=1)
+    def memory(capacity=4096):
+        mem = ReplayMemory(env, capacity, seed=1)
         g = torch.Generator(device=dev).manual_seed(2)
         mem.ring.copy_(torch.randn(mem.ring.shape, generator=g, device=dev))
         mem.ring[:, 10].tanh_()
         mem.ring[:, 22] = (mem.ring[:, 22] > -0.7).to(mem.ring.dtype)
-        mem.cursor[0] = 4096
+        mem.cursor[0] = capacity
         return mem
 
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -100,6 +115,8 @@ def main():
 
     if a.gradient:
         return finish(gradient_half(a, torch, env, _lib, learner, memory, interleaved))
+    if a.weight_gradient:
+        return finish(weight_gradient(a, torch, env, _lib, learner, memory, interleaved))
     hip, tor = learner("hip"), learner("torch")
     res = {"what": __doc__.split("\n\n")[0], "calls": a.calls, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0), "target": {}, "polyak": {}, "update": {}}
@@ -148,9 +165,87 @@ def main():
     finish(res)
 
 
+def step_calls(torch, env, _lib, h, B):
+    """The two gradient calls alone at batch B on learner h's blocks (its parameters move as in training):
+    critic_step(suffix) and policy_step(suffix) return the call of that entry point ("" or "_tiled")."""
+    from ctypes import byref
+    dev, dt = env.device, env.dtype
+    state, action, y = (torch.randn(B, 10, device=dev, dtype=dt), torch.rand(B, device=dev, dtype=dt) * 2 - 1,
+                        torch.randn(B, device=dev, dtype=dt))
+    ws = torch.empty(2 * B * _lib.SIT_SAC_WORKSPACE_ROW, dtype=torch.float32, device=dev)
+    c, p = _lib.SacCriticStepArgs(), _lib.SacPolicyStepArgs()
+    c.batch, c.workspace_floats = B, ws.numel()
+    c.critic_weights, c.critic_m, c.critic_v = h.online_weights.data_ptr(), h._m["critic"].data_ptr(), h._v["critic"].data_ptr()
+    c.state, c.action, c.y, c.workspace, c.results = (state.data_ptr(), action.data_ptr(), y.data_ptr(), ws.data_ptr(),
+                                                      h._results.data_ptr())
+    p.batch, p.tune, p.workspace_floats, p.seed, p.target_entropy = B, 1, ws.numel(), 1, -1.0
+    p.actor_weights, p.actor_m, p.actor_v = h.actor_weights.data_ptr(), h._m["policy"].data_ptr(), h._v["policy"].data_ptr()
+    p.critic_weights, p.alpha = h.online_weights.data_ptr(), h.alpha.data_ptr()
+    p.log_alpha, p.log_alpha_m, p.log_alpha_v = h.log_alpha.data_ptr(), h._m["alpha"].data_ptr(), h._v["alpha"].data_ptr()
+    p.state, p.workspace, p.results = state.data_ptr(), ws.data_ptr(), h._results.data_ptr()
+    n = {"u": 0}
+    keep = (state, action, y, ws)                  # the arguments hold addresses only
+
+    def critic_step(suffix=""):
+        def fn(keep=keep):
+            c.adam = h._adam("critic")
+            with torch.cuda.device(dev):
+                env._call("sit_sac_critic_step" + suffix, byref(c), env._stream())
+        return fn
+
+    def policy_step(suffix=""):
+        def fn(keep=keep):
+            n["u"] += 1
+            p.update, p.adam, p.alpha_adam = n["u"], h._adam("policy"), h._adam("alpha")
+            with torch.cuda.device(dev):
+                env._call("sit_sac_policy_step" + suffix, byref(p), env._stream())
+        return fn
+    return critic_step, policy_step
+
+
+def weight_gradient(a, torch, env, _lib, learner, memory, interleaved):
+    """The --weight-gradient measurement (see the module docstring)."""
+    batches = (64, 256, 1024, 4096, 16384)
+    capacity = 32768
+    res = {"what": "Cost of the tiled (MFMA) weight-gradient calls next to the plain ones, and of a whole update with "
+                   "weight_gradient='mfma' next to 'sum' (GPU).", "calls": a.calls, "warmup": a.warmup,
+           "device": torch.cuda.get_device_name(0), "ring_records": capacity, "batch": {}}
+    lrn = {"sum": learner("hip", "hip", "sum"), "mfma": learner("hip", "hip", "mfma")}
+    mems = {k: memory(capacity) for k in lrn}
+    count = {k: 0 for k in lrn}
+    h = learner("hip", "hip")
+
+    def update(mode, B):
+        def fn():
+            out = lrn[mode].update_parameters(mems[mode], B, count[mode])
+            count[mode] += 1
+            assert out is not None
+        return fn
+
+    def below(r, tiled, plain):
+        return r[tiled]["max_us"] < r[plain]["min_us"]
+    for B in batches:
+        assert len(mems["sum"]) > B
+        critic_step, policy_step = step_calls(torch, env, _lib, h, B)
+        r = interleaved({"sit_sac_critic_step": critic_step(), "sit_sac_critic_step_tiled": critic_step("_tiled"),
+                         "sit_sac_policy_step": policy_step(), "sit_sac_policy_step_tiled": policy_step("_tiled"),
+                         "update_sum": update("sum", B), "update_mfma": update("mfma", B)})
+        assert all(v == v for v in h._results.tolist())
+        r["tiled_range_below_plain"] = {"critic": below(r, "sit_sac_critic_step_tiled", "sit_sac_critic_step"),
+                                        "policy": below(r, "sit_sac_policy_step_tiled", "sit_sac_policy_step"),
+                                        "update": below(r, "update_mfma", "update_sum")}
+        r["plain_over_tiled_median"] = {
+            "critic": r["sit_sac_critic_step"]["median_us"] / r["sit_sac_critic_step_tiled"]["median_us"],
+            "policy": r["sit_sac_policy_step"]["median_us"] / r["sit_sac_policy_step_tiled"]["median_us"],
+            "update": r["update_sum"]["median_us"] / r["update_mfma"]["median_us"]}
+        res["batch"][str(B)] = r
+    res["tiled_calls_below_plain_at_every_batch_from_1024"] = all(
+        res["batch"][str(B)]["tiled_range_below_plain"][k] for B in batches if B >= 1024 for k in ("critic", "policy"))
+    return res
+
+
 def gradient_half(a, torch, env, _lib, learner, memory, interleaved):
     """The --gradient measurement (see the module docstring)."""
-    from ctypes import byref
     B = 64
     lrn = {"hip": learner("hip", "hip"), "torch": learner("hip", "torch")}
     mems = {k: memory() for k in lrn}
@@ -175,33 +270,8 @@ def gradient_half(a, torch, env, _lib, learner, memory, interleaved):
     res["update"] = r
     # ---- the two calls alone, on a third learner's blocks (its parameters move as in training) ----
     h = learner("hip", "hip")
-    dev, dt = env.device, env.dtype
-    state, action, y = (torch.randn(B, 10, device=dev, dtype=dt), torch.rand(B, device=dev, dtype=dt) * 2 - 1,
-                        torch.randn(B, device=dev, dtype=dt))
-    ws = torch.empty(2 * B * _lib.SIT_SAC_WORKSPACE_ROW, dtype=torch.float32, device=dev)
-    c, p = _lib.SacCriticStepArgs(), _lib.SacPolicyStepArgs()
-    c.batch, c.workspace_floats = B, ws.numel()
-    c.critic_weights, c.critic_m, c.critic_v = h.online_weights.data_ptr(), h._m["critic"].data_ptr(), h._v["critic"].data_ptr()
-    c.state, c.action, c.y, c.workspace, c.results = (state.data_ptr(), action.data_ptr(), y.data_ptr(), ws.data_ptr(),
-                                                      h._results.data_ptr())
-    p.batch, p.tune, p.workspace_floats, p.seed, p.target_entropy = B, 1, ws.numel(), 1, -1.0
-    p.actor_weights, p.actor_m, p.actor_v = h.actor_weights.data_ptr(), h._m["policy"].data_ptr(), h._v["policy"].data_ptr()
-    p.critic_weights, p.alpha = h.online_weights.data_ptr(), h.alpha.data_ptr()
-    p.log_alpha, p.log_alpha_m, p.log_alpha_v = h.log_alpha.data_ptr(), h._m["alpha"].data_ptr(), h._v["alpha"].data_ptr()
-    p.state, p.workspace, p.results = state.data_ptr(), ws.data_ptr(), h._results.data_ptr()
-    n = {"u": 0}
-
-    def critic_step():
-        c.adam = h._adam("critic")
-        with torch.cuda.device(dev):
-            env._call("sit_sac_critic_step", byref(c), env._stream())
-
-    def policy_step():
-        n["u"] += 1
-        p.update, p.adam, p.alpha_adam = n["u"], h._adam("policy"), h._adam("alpha")
-        with torch.cuda.device(dev):
-            env._call("sit_sac_policy_step", byref(p), env._stream())
-    res["calls_alone"] = interleaved({"sit_sac_critic_step": critic_step, "sit_sac_policy_step": policy_step,
+    critic_step, policy_step = step_calls(torch, env, _lib, h, B)
+    res["calls_alone"] = interleaved({"sit_sac_critic_step": critic_step(), "sit_sac_policy_step": policy_step(),
                                       "results_host_read": lambda: h._results.tolist()})
     assert all(v == v for v in h._results.tolist())
     res["host_read_share_of_hip_update"] = res["calls_alone"]["results_host_read"]["median_us"] / r["hip"]["median_us"]
