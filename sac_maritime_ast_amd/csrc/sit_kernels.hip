@@ -761,29 +761,32 @@ int64_t sit_sac_workspace_floats(int32_t batch) { return sac_workspace_floats(ba
 size_t sit_sac_critic_step_args_size(void) { return sizeof(sit_sac_critic_step_args); }
 size_t sit_sac_policy_step_args_size(void) { return sizeof(sit_sac_policy_step_args); }
 
+// tiled: the weight gradients as MFMA tiles (sit_sac_wgrad.h) instead of one sum per element
+static int sac_critic_step(sit_handle* h, const sit_sac_critic_step_args* a, bool tiled, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_critic_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  const SacAdamLaunch adam = sac_adam_launch<kSacIn, 1, 2, SIT_CRITIC_WEIGHTS, false>(tiled);
+  return with_real(h, [&](auto t) { return sac_launch_critic_step<decltype(t)>(h, a, adam, (hipStream_t)stream); });
+}
+
+static int sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, bool tiled, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  const SacAdamLaunch adam = sac_adam_launch<kActorObs, 2, 1, SIT_ACTOR_WEIGHTS, true>(tiled);
+  return with_real(h, [&](auto t) { return sac_launch_policy_step<decltype(t)>(h, a, adam, (hipStream_t)stream); });
+}
+
 int sit_sac_critic_step(sit_handle* h, const sit_sac_critic_step_args* a, void* stream) {
-  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
-  if (const char* why = sac_critic_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
-  return with_real(h, [&](auto t) { return sac_launch_critic_step<decltype(t)>(h, a, (hipStream_t)stream); });
+  return sac_critic_step(h, a, false, stream);
 }
-
 int sit_sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, void* stream) {
-  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
-  if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
-  return with_real(h, [&](auto t) { return sac_launch_policy_step<decltype(t)>(h, a, (hipStream_t)stream); });
+  return sac_policy_step(h, a, false, stream);
 }
-
-// the same two calls with the weight gradients as MFMA tiles (sit_sac_wgrad.h)
 int sit_sac_critic_step_tiled(sit_handle* h, const sit_sac_critic_step_args* a, void* stream) {
-  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
-  if (const char* why = sac_critic_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
-  return with_real(h, [&](auto t) { return sac_launch_critic_step_tiled<decltype(t)>(h, a, (hipStream_t)stream); });
+  return sac_critic_step(h, a, true, stream);
 }
-
 int sit_sac_policy_step_tiled(sit_handle* h, const sit_sac_policy_step_args* a, void* stream) {
-  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
-  if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
-  return with_real(h, [&](auto t) { return sac_launch_policy_step_tiled<decltype(t)>(h, a, (hipStream_t)stream); });
+  return sac_policy_step(h, a, true, stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,10 @@
 // the kernel is deterministic and rows [0, B) are the same bits for every B.  Rows past B in the last
 // block are computed on zeros and neither read nor written.
 //
+// The gradient half (sit_sac_grad.h, sit_sac_wgrad.h) builds on this file: its row kernels share sac_mlp,
+// sac_stage_rows and sac_gaussian_head, and the workspace record and the map from parameter segments to
+// record fields (sac_segment) are stated here, next to SacNet.
+//
 // Included from sit_kernels.hip only (the strictly compiled translation unit).
 #ifndef SIT_SAC_H
 #define SIT_SAC_H
@@ -43,6 +47,41 @@ static_assert(SacNet<kActorObs, 2>::kSize == SIT_ACTOR_WEIGHTS && SacNet<kActorO
 static_assert(SacNet<kSacIn, 1>::kSize <= SIT_CRITIC_WEIGHTS && SIT_CRITIC_WEIGHTS - SacNet<kSacIn, 1>::kSize < 4,
               "critic block: the packed network padded to 4 floats");
 static_assert(SacNet<kSacIn, 1>::W2T % 4 == 0, "float4 reads of the critic's W2^T");
+
+// A row's record in the float32 workspace of the gradient calls (sit_sac_grad.h writes it): x [12] (the
+// input row, zero padded), h1, h2 (the activations), d1, d2 (the deltas of the two hidden layers), then 4
+// floats: the output gradients g[0], g[1] and two per-row loss terms.
+constexpr int kWsX = 0, kWsXDim = 12;
+constexpr int kWsH1 = kWsX + kWsXDim, kWsH2 = kWsH1 + kActorHidden, kWsD1 = kWsH2 + kActorHidden;
+constexpr int kWsD2 = kWsD1 + kActorHidden, kWsG = kWsD2 + kActorHidden, kWsRow = kWsG + 4;
+static_assert(kWsRow == SIT_SAC_WORKSPACE_ROW, "the workspace row of include/sit.h");
+static_assert(kWsXDim == kSacIn + 1, "a record's input is SacLds::in's row");
+
+// Segment s = 0..5 of SacNet<IN, NOUT> (W1, b1, W2^T, b2, W3, b3) as its gradient reads the records: `out`
+// its offset in the block, rows x cols its row-major shape; element (r, c) is the sum over the batch of
+// (float row_at + r of a record) x (float col_at + c), an operand of width 0 being the constant 1.  The one
+// statement of which record fields make which parameter: k_sac_adam and k_sac_wgrad_adam both read it.
+struct SacSegment {
+  int out, rows, cols;
+  int row_at, row_n;
+  int col_at, col_n;
+};
+constexpr int kSacSegments = 6;
+
+template <int IN, int NOUT>
+constexpr SacSegment sac_segment(int s) {
+  using N = SacNet<IN, NOUT>;
+  constexpr int H = kActorHidden;
+  static_assert(IN <= kWsXDim && NOUT <= 2, "the record's x and g fields");
+  switch (s) {
+    case 0: return {N::W1, H, IN, kWsD1, H, kWsX, IN};
+    case 1: return {N::B1, 1, H, 0, 0, kWsD1, H};
+    case 2: return {N::W2T, H, H, kWsH1, H, kWsD2, H};
+    case 3: return {N::B2, 1, H, 0, 0, kWsD2, H};
+    case 4: return {N::W3, NOUT, H, kWsG, NOUT, kWsH2, H};
+    default: return {N::B3, NOUT, 1, kWsG, NOUT, 0, 0};
+  }
+}
 
 struct SacLds {
   float in[kSacRows][kSacIn + 1];                       // the rows' inputs: next_state, then a'
@@ -134,9 +173,22 @@ __device__ __forceinline__ void sac_mlp(const float* __restrict__ w, SacLds& S) 
   __syncthreads();
 }
 
-// standard normal of (seed, row, update): Philox4x32-10(key = seed, ctr = (row, 0x5441, update lo,
-// update hi)), then sampler_normal's Box-Muller step (sit_device.h)
-__device__ __forceinline__ double sac_normal(uint64_t seed, uint32_t row, uint64_t update, uint32_t tag = kSacTag) {
+// The block's rows [row0, row0 + nrow) of `state` into S.in, zeros past nrow; column kActorObs is the row's
+// `extra` (the critic step's action; nullptr: zero), the padding column zero.  The caller's barrier follows.
+template <typename T>
+__device__ __forceinline__ void sac_stage_rows(SacLds& S, const T* state, const T* extra, int row0, int nrow) {
+  const int j = threadIdx.x;
+  const int r = j / kActorObs, i = j % kActorObs;
+  if (j < kSacRows * kActorObs) S.in[r][i] = r < nrow ? (float)state[(size_t)(row0 + r) * kActorObs + i] : 0.0f;
+  if (j < kSacRows) {
+    S.in[j][kActorObs] = extra && j < nrow ? (float)extra[row0 + j] : 0.0f;
+    S.in[j][kActorObs + 1] = 0.0f;
+  }
+}
+
+// standard normal of (seed, row, update): Philox4x32-10(key = seed, ctr = (row, tag, update lo, update hi)),
+// then sampler_normal's Box-Muller step (sit_device.h)
+__device__ __forceinline__ double sac_normal(uint64_t seed, uint32_t row, uint64_t update, uint32_t tag) {
   uint32_t c[4] = {row, tag, (uint32_t)update, (uint32_t)(update >> 32)};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   const double u1 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6) + 1.0) * (1.0 / 9007199254740992.0);
@@ -147,7 +199,7 @@ __device__ __forceinline__ double sac_normal(uint64_t seed, uint32_t row, uint64
 // log(1 - tanh(x)^2 + 1e-6) without the cancellation of 1 - a * a: with em = expm1(2|x|) (formed as
 // actor_tanh forms it), 1 - tanh(x)^2 = 4 (em + 1) / (em + 2)^2, every factor a positive number known to
 // a few ulp.  |x| is capped at 40 (em < 6e34 stays finite; the term is below 1e-68 there, against 1e-6).
-// sac_one_minus_sq is 1 - tanh(x)^2 itself (the policy step's backward pass needs it too).
+// sac_one_minus_sq is 1 - tanh(x)^2 itself; sac_gaussian_head takes the logarithm.
 __device__ __forceinline__ float sac_one_minus_sq(float x) {
 #pragma clang fp reassociate(off) contract(off)
   const float ax = __builtin_fminf(__builtin_fabsf(x), 40.0f);
@@ -170,9 +222,30 @@ __device__ __forceinline__ float sac_one_minus_sq(float x) {
   return (4.0f * ((em + 1.0f) * rc)) * rc;              // (em + 1) / (em + 2) <= 1: no overflow
 }
 
-__device__ __forceinline__ float sac_log_one_minus_sq(float x) {
+// The squashed Gaussian head of row `row` = row0 + j from the actor's outputs S.head[2 j], S.head[2 j + 1]:
+// x = mu + exp(clip(ls_raw)) eps, the action tanh(x), s = 1 - tanh(x)^2 and the log-probability.  eps is the
+// caller's noise[row], or without one the draw of (seed, row, update, tag); a row that is not `live` (past
+// the batch) takes eps = 0.
+struct SacHead {
+  float mu, ls_raw, ls, eps, sig, x, act, s, logp;
+};
+
+template <typename T>
+__device__ __forceinline__ SacHead sac_gaussian_head(const SacLds& S, int j, int row, bool live, const T* noise,
+                                                     uint64_t seed, uint64_t update, uint32_t tag) {
 #pragma clang fp reassociate(off) contract(off)
-  return logf(sac_one_minus_sq(x) + 1e-6f);
+  SacHead h;
+  h.mu = S.head[2 * j];
+  h.ls_raw = S.head[2 * j + 1];
+  h.ls = __builtin_fminf(__builtin_fmaxf(h.ls_raw, -20.0f), 2.0f);
+  h.eps = 0.0f;
+  if (live) h.eps = noise ? (float)noise[row] : (float)sac_normal(seed, (uint32_t)row, update, tag);
+  h.sig = actor_exp(h.ls);
+  h.x = __builtin_fmaf(h.sig, h.eps, h.mu);
+  h.act = actor_tanh(h.x);
+  h.s = sac_one_minus_sq(h.x);
+  h.logp = ((-0.5f * (h.eps * h.eps) - h.ls) - 0.918938533f) - logf(h.s + 1e-6f);   // 0.5 log(2 pi)
+  return h;
 }
 
 template <typename T>
@@ -193,22 +266,15 @@ __global__ __launch_bounds__(256) void k_sac_target(const SacTarget<T> a) {
   const int j = threadIdx.x;
   const int row0 = blockIdx.x * R;
   const int nrow = min(R, a.batch - row0);    // >= 1: the grid is ceil(batch / R) blocks
-  {
-    const int r = j / kActorObs, i = j % kActorObs;
-    if (j < R * kActorObs) S.in[r][i] = r < nrow ? (float)a.next_state[(size_t)(row0 + r) * kActorObs + i] : 0.0f;
-    if (j < R) { S.in[j][kActorObs] = 0.0f; S.in[j][kActorObs + 1] = 0.0f; }
-  }
+  sac_stage_rows<T>(S, a.next_state, nullptr, row0, nrow);
   __syncthreads();
   sac_mlp<kActorObs, 2>(a.actor, S);
   // the squashed Gaussian head and its log-probability, thread j < R = row j (rows past nrow: on zeros)
   float logp = 0.0f, act = 0.0f;
   if (j < R) {
-    const float mu = S.head[2 * j], ls = __builtin_fminf(__builtin_fmaxf(S.head[2 * j + 1], -20.0f), 2.0f);
-    float eps = 0.0f;
-    if (j < nrow) eps = a.noise ? (float)a.noise[row0 + j] : (float)sac_normal(a.seed, (uint32_t)(row0 + j), a.update);
-    const float x = __builtin_fmaf(actor_exp(ls), eps, mu);
-    act = actor_tanh(x);
-    logp = ((-0.5f * (eps * eps) - ls) - 0.918938533f) - sac_log_one_minus_sq(x);   // 0.5 log(2 pi)
+    const SacHead hd = sac_gaussian_head(S, j, row0 + j, j < nrow, a.noise, a.seed, a.update, kSacTag);
+    act = hd.act;
+    logp = hd.logp;
     S.in[j][kActorObs] = act;
   }
   __syncthreads();

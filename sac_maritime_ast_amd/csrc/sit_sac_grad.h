@@ -3,16 +3,16 @@
 //
 // Two kernels per call.  k_sac_critic_fb / k_sac_policy_fb have the shape of k_sac_target (sit_sac.h): one
 // block of 256 threads per kSacRows minibatch rows, the networks one after another through the same LDS
-// by sac_mlp, then sac_mlp_backward in the same block (rows are independent).  Each block leaves its
-// rows' records in the caller's float32 workspace, kWsRow floats per row and network pass:
-//   x [12] (the input row, zero padded), h1 [256], h2 [256], d1 [256], d2 [256] (the deltas of the two
-//   hidden layers), then 4 floats: the output gradients g[0], g[1] and two per-row loss terms.
+// by sac_mlp, then sac_mlp_backward in the same block (rows are independent); staging the rows and the
+// squashed Gaussian head are sit_sac.h's (sac_stage_rows, sac_gaussian_head).  Each block leaves its rows'
+// records in the caller's float32 workspace, kWsRow floats per row and network pass (the layout: sit_sac.h,
+// next to SacNet).
 // k_sac_adam then runs one thread per element of a packed parameter block: the element's gradient is
-// the sum over b = 0 .. B-1, ascending, of (delta of its output unit) x (activation of its input unit),
-// read from the records, and Adam is applied to p, m, v in place; the gradient is never stored and the
-// padding floats of a block are not touched.  Thread 0 of one extra block adds up the per-row loss terms
-// in ascending row order (in float64), and in the actor's launch takes the temperature step and writes
-// lp, la, alpha.
+// the sum over b = 0 .. B-1, ascending, of the two record fields sac_segment (sit_sac.h) names for its
+// segment, (delta of its output unit) x (activation of its input unit), and Adam is applied to p, m, v in
+// place; the gradient is never stored and the padding floats of a block are not touched.  Thread 0 of one
+// extra block adds up the per-row loss terms in ascending row order (in float64); sac_finish_losses then
+// writes the losses and in the actor's launch takes the temperature step (lp, la, alpha).
 //
 // Backward layer 2 is a dot over a contiguous row of W2^T (thread k = input unit k).  Every sum has a
 // fixed order, there are no atomics, and no row's arithmetic depends on another row, so the result does
@@ -28,11 +28,6 @@
 namespace {
 
 constexpr uint32_t kSacPolicyTag = 0x5049u;   // counter word 1 of the policy loss's noise draw
-constexpr int kWsX = 0, kWsXDim = 12;
-constexpr int kWsH1 = kWsX + kWsXDim, kWsH2 = kWsH1 + kActorHidden, kWsD1 = kWsH2 + kActorHidden;
-constexpr int kWsD2 = kWsD1 + kActorHidden, kWsG = kWsD2 + kActorHidden, kWsRow = kWsG + 4;
-static_assert(kWsRow == SIT_SAC_WORKSPACE_ROW, "the workspace row of include/sit.h");
-static_assert(kWsXDim == kSacIn + 1, "a record's input is SacLds::in's row");
 
 struct SacGradLds {
   SacLds S;
@@ -94,6 +89,26 @@ __device__ __forceinline__ float* sac_ws_rows(float* ws, int batch, int pass, in
   return ws + ((size_t)pass * (size_t)batch + (size_t)row0) * kWsRow;
 }
 
+// two 256-wide fields of the block's records from their LDS arrays, thread j = unit j
+__device__ __forceinline__ void sac_store_fields(float* rec, int nrow, int at0, const float (&v0)[kSacRows][kActorHidden],
+                                                 int at1, const float (&v1)[kSacRows][kActorHidden]) {
+  const int j = threadIdx.x;
+  for (int r = 0; r < nrow; ++r) {
+    float* p = rec + (size_t)r * kWsRow;
+    p[at0 + j] = v0[r][j];
+    p[at1 + j] = v1[r][j];
+  }
+}
+
+// the x field of the block's records: columns [0, n) of S.in's rows, zeros behind them
+__device__ __forceinline__ void sac_store_x(float* rec, int nrow, const SacLds& S, int n) {
+  const int j = threadIdx.x;
+  if (j < kSacRows * kWsXDim) {
+    const int r = j / kWsXDim, i = j % kWsXDim;
+    if (r < nrow) rec[(size_t)r * kWsRow + kWsX + i] = i < n ? S.in[r][i] : 0.0f;
+  }
+}
+
 template <typename T>
 struct SacCriticFb {
   int batch;
@@ -111,11 +126,7 @@ __global__ __launch_bounds__(256) void k_sac_critic_fb(const SacCriticFb<T> a) {
   const int j = threadIdx.x;
   const int row0 = blockIdx.x * R;
   const int nrow = min(R, a.batch - row0);    // >= 1: the grid is ceil(batch / R) blocks
-  {
-    const int r = j / kActorObs, i = j % kActorObs;
-    if (j < R * kActorObs) S.in[r][i] = r < nrow ? (float)a.state[(size_t)(row0 + r) * kActorObs + i] : 0.0f;
-    if (j < R) { S.in[j][kActorObs] = j < nrow ? (float)a.action[row0 + j] : 0.0f; S.in[j][kActorObs + 1] = 0.0f; }
-  }
+  sac_stage_rows<T>(S, a.state, a.action, row0, nrow);
   const float yv = j < nrow ? (float)a.y[row0 + j] : 0.0f;
   __syncthreads();
 #pragma unroll 1
@@ -131,17 +142,9 @@ __global__ __launch_bounds__(256) void k_sac_critic_fb(const SacCriticFb<T> a) {
     __syncthreads();
     sac_mlp_backward<kSacIn, 1>(w, S, G.gout);
     float* rec = sac_ws_rows(a.ws, a.batch, c, row0);
-    for (int r = 0; r < nrow; ++r) {
-      float* p = rec + (size_t)r * kWsRow;
-      p[kWsH1 + j] = S.h1[r][j];
-      p[kWsH2 + j] = S.h2[r][j];
-      p[kWsD1 + j] = S.part[1][r][j];
-      p[kWsD2 + j] = S.part[0][r][j];
-    }
-    if (j < R * kWsXDim) {
-      const int r = j / kWsXDim, i = j % kWsXDim;
-      if (r < nrow) rec[(size_t)r * kWsRow + kWsX + i] = S.in[r][i];
-    }
+    sac_store_fields(rec, nrow, kWsH1, S.h1, kWsH2, S.h2);
+    sac_store_fields(rec, nrow, kWsD1, S.part[1], kWsD2, S.part[0]);
+    sac_store_x(rec, nrow, S, kWsXDim);
     if (j < nrow) {
       float* p = rec + (size_t)j * kWsRow + kWsG;
       p[0] = g; p[1] = 0.0f; p[2] = sq; p[3] = 0.0f;
@@ -169,38 +172,18 @@ __global__ __launch_bounds__(256) void k_sac_policy_fb(const SacPolicyFb<T> a) {
   const int row0 = blockIdx.x * R;
   const int nrow = min(R, a.batch - row0);
   float* rec = sac_ws_rows(a.ws, a.batch, 0, row0);
-  {
-    const int r = j / kActorObs, i = j % kActorObs;
-    if (j < R * kActorObs) S.in[r][i] = r < nrow ? (float)a.state[(size_t)(row0 + r) * kActorObs + i] : 0.0f;
-    if (j < R) { S.in[j][kActorObs] = 0.0f; S.in[j][kActorObs + 1] = 0.0f; }
-  }
+  sac_stage_rows<T>(S, a.state, nullptr, row0, nrow);
   __syncthreads();
   sac_mlp<kActorObs, 2>(a.actor, S);
   // the actor's activations go to the records now: the critics run through the same LDS
-  for (int r = 0; r < nrow; ++r) {
-    float* p = rec + (size_t)r * kWsRow;
-    p[kWsH1 + j] = S.h1[r][j];
-    p[kWsH2 + j] = S.h2[r][j];
-  }
-  if (j < R * kWsXDim) {
-    const int r = j / kWsXDim, i = j % kWsXDim;
-    // (column 10 of S.in receives the action below: the actor's record holds zeros there)
-    if (r < nrow) rec[(size_t)r * kWsRow + kWsX + i] = i < kActorObs ? S.in[r][i] : 0.0f;
-  }
+  // (column 10 of S.in receives the action below: the actor's record holds zeros there)
+  sac_store_fields(rec, nrow, kWsH1, S.h1, kWsH2, S.h2);
+  sac_store_x(rec, nrow, S, kActorObs);
   // the squashed Gaussian head, thread j < R = row j (rows past nrow: on zeros)
-  float eps = 0.0f, ls_raw = 0.0f, sig = 0.0f, act = 0.0f, s = 0.0f, logp = 0.0f;
+  SacHead hd{};
   if (j < R) {
-    const float mu = S.head[2 * j];
-    ls_raw = S.head[2 * j + 1];
-    const float ls = __builtin_fminf(__builtin_fmaxf(ls_raw, -20.0f), 2.0f);
-    if (j < nrow)
-      eps = a.noise ? (float)a.noise[row0 + j] : (float)sac_normal(a.seed, (uint32_t)(row0 + j), a.update, kSacPolicyTag);
-    sig = actor_exp(ls);
-    const float x = __builtin_fmaf(sig, eps, mu);
-    act = actor_tanh(x);
-    s = sac_one_minus_sq(x);
-    logp = ((-0.5f * (eps * eps) - ls) - 0.918938533f) - logf(s + 1e-6f);   // 0.5 log(2 pi)
-    S.in[j][kActorObs] = act;
+    hd = sac_gaussian_head(S, j, row0 + j, j < nrow, a.noise, a.seed, a.update, kSacPolicyTag);
+    S.in[j][kActorObs] = hd.act;
   }
   __syncthreads();
   // both critics at (state, a), each taken back to the action input from an output gradient of -1/B
@@ -237,15 +220,15 @@ __global__ __launch_bounds__(256) void k_sac_policy_fb(const SacPolicyFb<T> a) {
     const bool first = q[0] <= q[1];
     const float gsel = first ? ga[0] : ga[1], qmin = first ? q[0] : q[1];
     const float ab = alpha / (float)a.batch;
-    const float dx = ab * (((2.0f * act) * s) / (s + 1e-6f)) + gsel * s;
-    float dmu = dx, dls = (dx * sig) * eps - ab;
-    if (ls_raw < -20.0f || ls_raw > 2.0f) dls = 0.0f;
+    const float dx = ab * (((2.0f * hd.act) * hd.s) / (hd.s + 1e-6f)) + gsel * hd.s;
+    float dmu = dx, dls = (dx * hd.sig) * hd.eps - ab;
+    if (hd.ls_raw < -20.0f || hd.ls_raw > 2.0f) dls = 0.0f;
     if (j >= nrow) { dmu = 0.0f; dls = 0.0f; }
     G.gout[2 * j] = dmu;
     G.gout[2 * j + 1] = dls;
     if (j < nrow) {
       float* p = rec + (size_t)j * kWsRow + kWsG;
-      p[0] = dmu; p[1] = dls; p[2] = alpha * logp - qmin; p[3] = logp;
+      p[0] = dmu; p[1] = dls; p[2] = alpha * hd.logp - qmin; p[3] = hd.logp;
     }
   }
   // the actor's activations back from the records (each thread reads what it wrote)
@@ -257,11 +240,7 @@ __global__ __launch_bounds__(256) void k_sac_policy_fb(const SacPolicyFb<T> a) {
   }
   __syncthreads();
   sac_mlp_backward<kActorObs, 2>(a.actor, S, G.gout);
-  for (int r = 0; r < nrow; ++r) {
-    float* p = rec + (size_t)r * kWsRow;
-    p[kWsD1 + j] = S.part[1][r][j];
-    p[kWsD2 + j] = S.part[0][r][j];
-  }
+  sac_store_fields(rec, nrow, kWsD1, S.part[1], kWsD2, S.part[0]);
 }
 
 struct SacAdamScalars {
@@ -290,64 +269,74 @@ struct SacAdam {
   SacAdamScalars oa;
 };
 
+// What follows the loss sums of network pass c: `sum` of the rows' loss terms gives results[c], or in the
+// actor's launch (TEMPERATURE) results[2], and there `ent` = sum of (logp + target_entropy) gives the
+// temperature loss, log_alpha's Adam step and alpha = exp(log_alpha): results[3], results[4].  One thread.
+template <bool TEMPERATURE>
+__device__ __forceinline__ void sac_finish_losses(const SacAdam& a, int c, double sum, double ent) {
+#pragma clang fp reassociate(off) contract(off)
+  const double B = (double)a.batch;
+  if (!TEMPERATURE) {
+    a.results[c] = (float)(sum / B);
+    return;
+  }
+  a.results[2] = (float)(sum / B);
+  float la = 0.0f;
+  if (a.tune) {
+    const double mean = ent / B;
+    la = (float)-((double)*a.log_alpha * mean);
+    sac_adam_apply(a.oa, (float)-mean, a.log_alpha, a.log_alpha_m, a.log_alpha_v);
+    *a.alpha = expf(*a.log_alpha);
+  }
+  a.results[3] = la;
+  a.results[4] = *a.alpha;
+}
+
 // NETS networks of SacNet<IN, NOUT>, STRIDE floats apart (the records of network c are pass c).
 // TEMPERATURE: the actor's launch (results[2..4] and the temperature step) instead of the critics'
 // (results[0..1]).
 template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE>
 __global__ __launch_bounds__(256) void k_sac_adam(const SacAdam a) {
 #pragma clang fp reassociate(off) contract(off)
-  using N = SacNet<IN, NOUT>;
-  constexpr int H = kActorHidden;
+  static_assert(!TEMPERATURE || NETS == 1, "the temperature step belongs to the actor's launch");
   constexpr unsigned kBlocks = (NETS * STRIDE + 255) / 256;
   const int B = a.batch;
   if (blockIdx.x == kBlocks) {                 // the extra block: the losses
     if (threadIdx.x != 0) return;
     // (one thread, so the sums over the rows are kept in float64: a float32 running sum of B terms loses
     // about sqrt(B) ulp, more than the pairwise sums of a library reduction)
-    if (!TEMPERATURE) {
-      for (int c = 0; c < NETS; ++c) {
-        const float* g = a.ws + (size_t)c * (size_t)B * kWsRow + kWsG;
-        double sum = 0.0;
-        for (int b = 0; b < B; ++b) sum += (double)g[(size_t)b * kWsRow + 2];
-        a.results[c] = (float)(sum / (double)B);
-      }
-    } else {
-      const float* g = a.ws + kWsG;
+    for (int c = 0; c < NETS; ++c) {
+      const float* g = a.ws + (size_t)c * (size_t)B * kWsRow + kWsG;
       double sum = 0.0, ent = 0.0;
       for (int b = 0; b < B; ++b) {
         sum += (double)g[(size_t)b * kWsRow + 2];
-        ent += (double)g[(size_t)b * kWsRow + 3] + (double)a.target_entropy;
+        if (TEMPERATURE) ent += (double)g[(size_t)b * kWsRow + 3] + (double)a.target_entropy;
       }
-      a.results[2] = (float)(sum / (double)B);
-      float la = 0.0f;
-      if (a.tune) {
-        const double mean = ent / (double)B;
-        la = (float)-((double)*a.log_alpha * mean);
-        sac_adam_apply(a.oa, (float)-mean, a.log_alpha, a.log_alpha_m, a.log_alpha_v);
-        *a.alpha = expf(*a.log_alpha);
-      }
-      a.results[3] = la;
-      a.results[4] = *a.alpha;
+      sac_finish_losses<TEMPERATURE>(a, c, sum, ent);
     }
     return;
   }
   const int e = blockIdx.x * 256 + threadIdx.x;
   const int c = e / STRIDE, off = e % STRIDE;
-  if (c >= NETS || off >= N::kSize) return;    // past the block, or its padding
-  // the element's gradient: sum_b d[b] * x[b] (x == nullptr: a bias, x = 1)
-  int d_at, x_at = -1;
-  if (off < N::B1) { d_at = kWsD1 + off / IN; x_at = kWsX + off % IN; }
-  else if (off < N::W2T) { d_at = kWsD1 + (off - N::B1); }
-  else if (off < N::B2) { d_at = kWsD2 + (off - N::W2T) % H; x_at = kWsH1 + (off - N::W2T) / H; }
-  else if (off < N::W3) { d_at = kWsD2 + (off - N::B2); }
-  else if (off < N::B3) { d_at = kWsG + (off - N::W3) / H; x_at = kWsH2 + (off - N::W3) % H; }
-  else { d_at = kWsG + (off - N::B3); }
+  if (c >= NETS || off >= SacNet<IN, NOUT>::kSize) return;    // past the block, or its padding
+  // the element's gradient: the sum over the rows of its segment's two operands (sac_segment)
+  int row_at = -1, col_at = -1;
+#pragma unroll
+  for (int s = 0; s < kSacSegments; ++s) {
+    const SacSegment g = sac_segment<IN, NOUT>(s);
+    if (off >= g.out && off < g.out + g.rows * g.cols) {
+      if (g.row_n) row_at = g.row_at + (off - g.out) / g.cols;
+      if (g.col_n) col_at = g.col_at + (off - g.out) % g.cols;
+    }
+  }
   const float* rec = a.ws + (size_t)c * (size_t)B * kWsRow;
   float g = 0.0f;
-  if (x_at >= 0) {
-    for (int b = 0; b < B; ++b) g = __builtin_fmaf(rec[(size_t)b * kWsRow + d_at], rec[(size_t)b * kWsRow + x_at], g);
-  } else {
-    for (int b = 0; b < B; ++b) g += rec[(size_t)b * kWsRow + d_at];
+  if (row_at >= 0 && col_at >= 0) {
+    // (the column operand first: in W2^T, most of a block, it is the load a wave coalesces)
+    for (int b = 0; b < B; ++b) g = __builtin_fmaf(rec[(size_t)b * kWsRow + col_at], rec[(size_t)b * kWsRow + row_at], g);
+  } else {                                     // a bias: the other operand is the constant 1
+    const int at = row_at >= 0 ? row_at : col_at;
+    for (int b = 0; b < B; ++b) g += rec[(size_t)b * kWsRow + at];
   }
   sac_adam_apply(a.o, g, a.p + e, a.m + e, a.v + e);
 }
@@ -363,10 +352,21 @@ inline SacAdamScalars sac_adam_scalars(const sit_sac_adam& o) {
   return s;
 }
 
-// The two halves of each call, apart: the row kernel's launch and the arguments of the Adam kernel that
-// follows it (k_sac_adam here, k_sac_wgrad_adam of sit_sac_wgrad.h in the _tiled calls).
+// The Adam kernel that follows a call's row kernel, with its grid: k_sac_adam here, or k_sac_wgrad_adam of
+// sit_sac_wgrad.h in the _tiled calls (sac_adam_launch there picks one).
+struct SacAdamLaunch {
+  void (*kernel)(const SacAdam);
+  unsigned blocks, threads;
+};
+
+inline int sac_launch_adam(sit_handle* h, const SacAdamLaunch& k, const SacAdam& a, hipStream_t stream) {
+  hipLaunchKernelGGL(k.kernel, dim3(k.blocks), dim3(k.threads), 0, stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return SIT_OK;
+}
+
 template <typename T>
-int sac_launch_critic_fb(sit_handle* h, const sit_sac_critic_step_args* s, hipStream_t stream) {
+int sac_launch_critic_step(sit_handle* h, const sit_sac_critic_step_args* s, const SacAdamLaunch& adam, hipStream_t stream) {
   SacCriticFb<T> f{};
   f.batch = s->batch;
   f.critic = s->critic_weights;
@@ -376,32 +376,17 @@ int sac_launch_critic_fb(sit_handle* h, const sit_sac_critic_step_args* s, hipSt
   f.ws = s->workspace;
   hipLaunchKernelGGL(k_sac_critic_fb<T>, dim3((unsigned)((s->batch + kSacRows - 1) / kSacRows)), dim3(256), 0, stream, f);
   HIP_TRY(h, hipGetLastError());
-  return SIT_OK;
-}
-
-inline SacAdam sac_critic_adam_args(const sit_sac_critic_step_args* s) {
   SacAdam a{};
   a.batch = s->batch;
   a.p = s->critic_weights; a.m = s->critic_m; a.v = s->critic_v;
   a.ws = s->workspace;
   a.results = s->results;
   a.o = sac_adam_scalars(s->adam);
-  return a;
+  return sac_launch_adam(h, adam, a, stream);
 }
 
 template <typename T>
-int sac_launch_critic_step(sit_handle* h, const sit_sac_critic_step_args* s, hipStream_t stream) {
-  constexpr int kElems = 2 * SIT_CRITIC_WEIGHTS;
-  if (const int rc = sac_launch_critic_fb<T>(h, s, stream)) return rc;
-  const SacAdam a = sac_critic_adam_args(s);
-  hipLaunchKernelGGL((k_sac_adam<kSacIn, 1, 2, SIT_CRITIC_WEIGHTS, false>), dim3((kElems + 255) / 256 + 1), dim3(256), 0,
-                     stream, a);
-  HIP_TRY(h, hipGetLastError());
-  return SIT_OK;
-}
-
-template <typename T>
-int sac_launch_policy_fb(sit_handle* h, const sit_sac_policy_step_args* s, hipStream_t stream) {
+int sac_launch_policy_step(sit_handle* h, const sit_sac_policy_step_args* s, const SacAdamLaunch& adam, hipStream_t stream) {
   SacPolicyFb<T> f{};
   f.batch = s->batch;
   f.seed = s->seed;
@@ -414,10 +399,6 @@ int sac_launch_policy_fb(sit_handle* h, const sit_sac_policy_step_args* s, hipSt
   f.ws = s->workspace;
   hipLaunchKernelGGL(k_sac_policy_fb<T>, dim3((unsigned)((s->batch + kSacRows - 1) / kSacRows)), dim3(256), 0, stream, f);
   HIP_TRY(h, hipGetLastError());
-  return SIT_OK;
-}
-
-inline SacAdam sac_policy_adam_args(const sit_sac_policy_step_args* s) {
   SacAdam a{};
   a.batch = s->batch;
   a.p = s->actor_weights; a.m = s->actor_m; a.v = s->actor_v;
@@ -431,17 +412,7 @@ inline SacAdam sac_policy_adam_args(const sit_sac_policy_step_args* s) {
     a.log_alpha = s->log_alpha; a.log_alpha_m = s->log_alpha_m; a.log_alpha_v = s->log_alpha_v;
     a.oa = sac_adam_scalars(s->alpha_adam);
   }
-  return a;
-}
-
-template <typename T>
-int sac_launch_policy_step(sit_handle* h, const sit_sac_policy_step_args* s, hipStream_t stream) {
-  if (const int rc = sac_launch_policy_fb<T>(h, s, stream)) return rc;
-  const SacAdam a = sac_policy_adam_args(s);
-  hipLaunchKernelGGL((k_sac_adam<kActorObs, 2, 1, SIT_ACTOR_WEIGHTS, true>), dim3((SIT_ACTOR_WEIGHTS + 255) / 256 + 1),
-                     dim3(256), 0, stream, a);
-  HIP_TRY(h, hipGetLastError());
-  return SIT_OK;
+  return sac_launch_adam(h, adam, a, stream);
 }
 
 }  // namespace

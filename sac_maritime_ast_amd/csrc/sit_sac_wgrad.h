@@ -10,11 +10,12 @@
 // bits.  A bias is the same chain with the other operand fixed at 1.0f (fmaf(d, 1, g) is g + d rounded
 // once) and takes a tile of its own.
 //
-// Tiles of SacNet<IN, NOUT>, T = 256 / 32 = 8 (97 per network), rows x columns; the column index is the
-// contiguous index of the packed block:
-//   W2^T  T x T tiles  A = h1[b][32 kt + i]   B = d2[b][32 nt + j]
+// Tiles of SacNet<IN, NOUT>: each segment of sac_segment (sit_sac.h, the map k_sac_adam reads too) cut into
+// 32 x 32 tiles, rows x columns, the column index the contiguous index of the packed block; T = 256 / 32 = 8,
+// 97 tiles per network, in the block's order:
 //   W1    T tiles      A = d1[b][32 jt + i]   B = x[b][j], j < IN
 //   b1    T tiles      A = 1 (row 0 is kept)  B = d1[b][32 jt + j]
+//   W2^T  T x T tiles  A = h1[b][32 kt + i]   B = d2[b][32 nt + j]
 //   b2    T tiles      A = 1                  B = d2[b][32 nt + j]
 //   W3    T tiles      A = g[b][i], i < NOUT  B = h2[b][32 nt + j]
 //   b3    1 tile       A = g[b][i], i < NOUT  B = 1 (column 0 is kept)
@@ -33,7 +34,8 @@
 // touched.
 //
 // The losses: one wave per network pass behind the tiles.  64 rows' terms are fetched at a time, one per
-// lane, and added in ascending row order in float64 as k_sac_adam's thread 0 adds them.
+// lane, and added in ascending row order in float64 as k_sac_adam's thread 0 adds them; lane 0 then calls the
+// same sac_finish_losses (sit_sac_grad.h).
 //
 // Included from sit_kernels.hip only (the strictly compiled translation unit).
 #ifndef SIT_SAC_WGRAD_H
@@ -48,8 +50,7 @@ typedef float SacAcc __attribute__((ext_vector_type(16)));
 constexpr int kWgGroup = 16;                       // MFMAs per prefetch group
 constexpr int kWgGroupRows = 2 * kWgGroup;
 constexpr int kWgT = kActorHidden / 32;            // tiles along a hidden dimension
-constexpr int kWgTiles = kWgT * kWgT + 4 * kWgT + 1;
-static_assert(kActorHidden % 32 == 0, "whole tiles along the hidden dimension");
+constexpr int kWgTiles = kWgT * kWgT + 4 * kWgT + 1;   // W2^T, then W1, b1, b2, W3 a strip each, and b3
 static_assert(kWsXDim <= 32 && 2 * kWgGroup <= 63, "x fits a tile; a group's loads fit the counter");
 
 struct SacWgradTile {
@@ -58,24 +59,30 @@ struct SacWgradTile {
   int out, stride, rows, cols;  // the tile's corner in the block, its row stride, the part that is kept
 };
 
+// Tile t of a network: the segments of sac_segment in order, each cut into 32 x 32 tiles, row-major.
+template <int IN, int NOUT>
+constexpr int sac_wgrad_tiles(int segments) {      // the tiles of segments [0, segments)
+  int n = 0;
+  for (int s = 0; s < segments; ++s) n += ((sac_segment<IN, NOUT>(s).rows + 31) / 32) * ((sac_segment<IN, NOUT>(s).cols + 31) / 32);
+  return n;
+}
+
 template <int IN, int NOUT>
 __device__ __forceinline__ SacWgradTile sac_wgrad_tile(int t) {
-  using N = SacNet<IN, NOUT>;
-  constexpr int H = kActorHidden, T = kWgT;
-  static_assert(IN <= kWsXDim && NOUT <= 2, "the record's x and g fields");
-  if (t < T * T) {
-    const int kt = t / T, nt = t % T;
-    return {kWsH1 + 32 * kt, 32, kWsD2 + 32 * nt, 32, N::W2T + 32 * kt * H + 32 * nt, H, 32, 32};
+  static_assert(sac_wgrad_tiles<IN, NOUT>(kSacSegments) == kWgTiles, "the grid's tile blocks per network");
+  constexpr auto width = [](int n, int at) { return n - at < 32 ? n - at : 32; };   // of a tile that starts at `at`
+  SacWgradTile d{};
+#pragma unroll
+  for (int s = 0; s < kSacSegments; ++s) {
+    const SacSegment g = sac_segment<IN, NOUT>(s);
+    const int first = sac_wgrad_tiles<IN, NOUT>(s), across = (g.cols + 31) / 32;
+    if (t >= first && t < sac_wgrad_tiles<IN, NOUT>(s + 1)) {
+      const int r0 = 32 * ((t - first) / across), c0 = 32 * ((t - first) % across);
+      d = {g.row_at + r0, g.row_n ? width(g.row_n, r0) : 0, g.col_at + c0, g.col_n ? width(g.col_n, c0) : 0,
+           g.out + r0 * g.cols + c0, g.cols, width(g.rows, r0), width(g.cols, c0)};
+    }
   }
-  t -= T * T;
-  const int i = t % T;
-  switch (t / T) {
-    case 0: return {kWsD1 + 32 * i, 32, kWsX, IN, N::W1 + 32 * i * IN, IN, 32, IN};
-    case 1: return {0, 0, kWsD1 + 32 * i, 32, N::B1 + 32 * i, 0, 1, 32};
-    case 2: return {0, 0, kWsD2 + 32 * i, 32, N::B2 + 32 * i, 0, 1, 32};
-    case 3: return {kWsG, NOUT, kWsH2 + 32 * i, 32, N::W3 + 32 * i, H, NOUT, 32};
-    default: return {kWsG, NOUT, 0, 0, N::B3, 1, NOUT, 1};
-  }
+  return d;
 }
 
 // A lane's side of the K loop: pa / pb are its A and B addresses in the record of row `half` (lanes past an
@@ -184,21 +191,7 @@ __global__ __launch_bounds__(64) void k_sac_wgrad_adam(const SacAdam a) {
     const int c = blk - NETS * kWgTiles;
     double sum = 0.0, ent = 0.0;
     sac_wgrad_loss_sums<TEMPERATURE>(a.ws + (size_t)c * (size_t)B * kWsRow + kWsG, B, a.target_entropy, sum, ent);
-    if (threadIdx.x != 0) return;
-    if (!TEMPERATURE) {
-      a.results[c] = (float)(sum / (double)B);
-    } else {
-      a.results[2] = (float)(sum / (double)B);
-      float la = 0.0f;
-      if (a.tune) {
-        const double mean = ent / (double)B;
-        la = (float)-((double)*a.log_alpha * mean);
-        sac_adam_apply(a.oa, (float)-mean, a.log_alpha, a.log_alpha_m, a.log_alpha_v);
-        *a.alpha = expf(*a.log_alpha);
-      }
-      a.results[3] = la;
-      a.results[4] = *a.alpha;
-    }
+    if (threadIdx.x == 0) sac_finish_losses<TEMPERATURE>(a, c, sum, ent);
     return;
   }
   const int c = blk / kWgTiles;
@@ -257,24 +250,11 @@ __global__ __launch_bounds__(64) void k_sac_wgrad_adam(const SacAdam a) {
   }
 }
 
-template <typename T>
-int sac_launch_critic_step_tiled(sit_handle* h, const sit_sac_critic_step_args* s, hipStream_t stream) {
-  if (const int rc = sac_launch_critic_fb<T>(h, s, stream)) return rc;
-  const SacAdam a = sac_critic_adam_args(s);
-  hipLaunchKernelGGL((k_sac_wgrad_adam<kSacIn, 1, 2, SIT_CRITIC_WEIGHTS, false>), dim3(2 * kWgTiles + 2), dim3(64), 0,
-                     stream, a);
-  HIP_TRY(h, hipGetLastError());
-  return SIT_OK;
-}
-
-template <typename T>
-int sac_launch_policy_step_tiled(sit_handle* h, const sit_sac_policy_step_args* s, hipStream_t stream) {
-  if (const int rc = sac_launch_policy_fb<T>(h, s, stream)) return rc;
-  const SacAdam a = sac_policy_adam_args(s);
-  hipLaunchKernelGGL((k_sac_wgrad_adam<kActorObs, 2, 1, SIT_ACTOR_WEIGHTS, true>), dim3(kWgTiles + 1), dim3(64), 0,
-                     stream, a);
-  HIP_TRY(h, hipGetLastError());
-  return SIT_OK;
+// the Adam kernel of a call and its grid: the tiled one here, or k_sac_adam (sit_sac_grad.h)
+template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE>
+inline SacAdamLaunch sac_adam_launch(bool tiled) {
+  if (!tiled) return {k_sac_adam<IN, NOUT, NETS, STRIDE, TEMPERATURE>, (NETS * STRIDE + 255) / 256 + 1, 256};
+  return {k_sac_wgrad_adam<IN, NOUT, NETS, STRIDE, TEMPERATURE>, NETS * kWgTiles + NETS, 64};
 }
 
 }  // namespace

@@ -39,7 +39,7 @@ from torch import nn
 
 from . import _lib
 from .replay import philox4x32_10
-from .samplers import EPS, LOG_SIG_CAP_MAX, LOG_SIG_CAP_MIN, pack_actor_weights
+from .samplers import EPS, LOG_SIG_CAP_MAX, LOG_SIG_CAP_MIN, block_segments, pack_actor_weights
 
 OBS, H = _lib.SIT_OBS_DIM, _lib.SIT_ACTOR_HIDDEN
 CRITIC_IN = _lib.SIT_CRITIC_INPUT
@@ -84,14 +84,13 @@ def _critic_layers(q: nn.Module):
     return out
 
 
-def _critic_segments(layers):
-    """(parameter view, shape in the block, offset) of both critics' blocks; W2 goes in transposed."""
-    for c, (l1, l2, l3) in enumerate(layers):
-        o = c * CRITIC_WEIGHTS
-        for t, shape in ((l1.weight, (H, CRITIC_IN)), (l1.bias, (H,)), (l2.weight.t(), (H, H)), (l2.bias, (H,)),
-                         (l3.weight, (1, H)), (l3.bias, (1,))):
-            yield t, shape, o
-            o += t.numel()
+def _block_and_parameters(block: torch.Tensor, layers):
+    """(view into the packed block, parameter) pairs in ``parameters()`` order; `layers` as for ``block_views``."""
+    flat = block.view(-1)
+    for c, net in enumerate(layers):
+        n_in, n_out = net[0].weight.shape[1], net[2].weight.shape[0]
+        for layer, name, seg in block_segments(flat, n_in, n_out, c * CRITIC_WEIGHTS):
+            yield seg, getattr(net[layer], name)
 
 
 def pack_critic_weights(q: nn.Module, out: torch.Tensor | None = None) -> torch.Tensor | None:
@@ -109,9 +108,8 @@ def pack_critic_weights(q: nn.Module, out: torch.Tensor | None = None) -> torch.
         elif out.numel() != 2 * CRITIC_WEIGHTS or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError(f"pack_critic_weights: out must be a contiguous float32 tensor of {2 * CRITIC_WEIGHTS} "
                              f"elements (got {tuple(out.shape)} {out.dtype}, contiguous={out.is_contiguous()})")
-        flat = out.view(-1)
-        for t, shape, o in _critic_segments(layers):
-            flat[o:o + t.numel()].view(shape).copy_(t.detach())
+        for seg, p in _block_and_parameters(out, layers):
+            seg.copy_(p.detach())
     return out
 
 
@@ -121,9 +119,8 @@ def unpack_critic_weights(block: torch.Tensor, q: nn.Module) -> nn.Module:
     if layers is None or block.numel() != 2 * CRITIC_WEIGHTS:
         raise ValueError("unpack_critic_weights: a twin 11 -> 256 -> 256 -> 1 critic and its packed block are required")
     with torch.no_grad():
-        flat = block.reshape(-1)
-        for t, shape, o in _critic_segments(layers):
-            t.copy_(flat[o:o + t.numel()].view(shape))
+        for seg, p in _block_and_parameters(block.reshape(-1), layers):
+            p.copy_(seg)
     return q
 
 
@@ -138,18 +135,9 @@ def _actor_layers(policy: nn.Module):
 def block_views(block: torch.Tensor, layers) -> list:
     """Views into a packed block (or a moment block of the same layout), one per parameter in
     ``parameters()`` order and of the parameter's shape: `layers` is ``[(l1, l2, l3)]`` of the actor or
-    ``_critic_layers(q)`` of the twin critic.  l2.weight's view is the transpose of its W2^T segment."""
-    flat, out, o = block.view(-1), [], 0
-    stride = CRITIC_WEIGHTS if len(layers) == 2 else 0
-    for c, (l1, l2, l3) in enumerate(layers):
-        o = c * stride
-        for p, transposed in ((l1.weight, False), (l1.bias, False), (l2.weight, True), (l2.bias, False),
-                              (l3.weight, False), (l3.bias, False)):
-            n = p.numel()
-            seg = flat[o:o + n]
-            out.append(seg.view(p.shape[1], p.shape[0]).t() if transposed else seg.view(p.shape))
-            o += n
-    return out
+    ``_critic_layers(q)`` of the twin critic.  l2.weight's view is the transpose of its W2^T segment.
+    layers None: the block is one parameter by itself (log_alpha's moments)."""
+    return [block] if layers is None else [seg for seg, _ in _block_and_parameters(block, layers)]
 
 
 def bind_parameters(block: torch.Tensor, layers) -> list:
@@ -226,16 +214,9 @@ def policy_noise(seed: int, update: int, batch: int) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------
 def _mlp64(w: np.ndarray, n_in: int, n_out: int, x: np.ndarray) -> np.ndarray:
     """A packed (n_in -> 256 -> 256 -> n_out) block applied to x [B, n_in] in float64."""
-    w = np.asarray(w, dtype=np.float64)
-    o = 0
-    w1 = w[o:o + H * n_in].reshape(H, n_in); o += H * n_in
-    b1 = w[o:o + H]; o += H
-    w2t = w[o:o + H * H].reshape(H, H); o += H * H
-    b2 = w[o:o + H]; o += H
-    w3 = w[o:o + n_out * H].reshape(n_out, H); o += n_out * H
-    b3 = w[o:o + n_out]
+    w1, b1, w2, b2, w3, b3 = (seg for _, _, seg in block_segments(np.asarray(w, dtype=np.float64), n_in, n_out))
     h = np.maximum(x @ w1.T + b1, 0.0)
-    h = np.maximum(h @ w2t + b2, 0.0)
+    h = np.maximum(h @ w2.T + b2, 0.0)
     return h @ w3.T + b3
 
 
@@ -291,10 +272,6 @@ def torch_target(policy, target_critic, next_state, reward, mask, eps, alpha, ga
         return {"y": y, "next_action": a, "next_logp": logp, "q1": q1, "q2": q2}
 
 
-def _torch_target(*args):
-    return torch_target(*args)["y"]
-
-
 def _sample(memory, batch_size):
     """One minibatch of a ReplayMemory (device tensors) or a ReplayReference (NumPy) as [B, ...] items."""
     b = memory.sample(batch_size)
@@ -329,7 +306,29 @@ def _gradient_half(pol, critic, optims, log_alpha, alpha, auto, batch, y, eps_pi
     return l1.detach(), l2.detach(), lp.detach(), la.detach(), alpha
 
 
-class SacLearner:
+class _SacState:
+    """What ``SacLearner`` and ``SacUpdateReference`` set up alike: the hyper-parameters, log_alpha and alpha
+    (tensors of one element in the networks' dtype and on their device) and the Adam optimisers."""
+
+    def _setup(self, dtype, device, *, gamma, tau, lr, alpha, automatic_entropy_tuning, target_update_interval,
+               reward_scale, seed):
+        self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
+        self.target_update_interval, self.seed = int(target_update_interval), int(seed)
+        self.auto = bool(automatic_entropy_tuning)
+        self.log_alpha = torch.full((1,), math.log(alpha), dtype=dtype, device=device, requires_grad=self.auto)
+        self.alpha = self.log_alpha.detach().exp()
+        self.optims = {"critic": torch.optim.Adam(self.critic.parameters(), lr=lr),
+                       "policy": torch.optim.Adam(self.policy.parameters(), lr=lr)}
+        if self.auto:
+            self.optims["alpha"] = torch.optim.Adam([self.log_alpha], lr=lr)
+
+    def _polyak_torch(self):
+        with torch.no_grad():
+            for t, p in zip(self.target_critic.parameters(), self.critic.parameters()):
+                t.add_(p - t, alpha=self.tau)
+
+
+class SacLearner(_SacState):
     """SAC updates on the device of one ``VecMultiShipRLEnv`` from its ``ReplayMemory``.
 
     `policy` is the ``GaussianPolicy`` the samplers serve (float32, on the env's device); the learner
@@ -374,17 +373,12 @@ class SacLearner:
         self.weight_gradient = weight_gradient
         self.env, self.policy, self.target, self.gradient = env, policy, target, gradient
         self.lr, self.target_entropy = float(lr), -1.0
-        self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
-        self.target_update_interval, self.seed = int(target_update_interval), int(seed)
-        self.auto = bool(automatic_entropy_tuning)
         dev = env.device
         self.critic = (critic if critic is not None else QNetwork()).to(device=dev, dtype=torch.float32)
-        self.log_alpha = torch.full((1,), math.log(alpha), dtype=torch.float32, device=dev, requires_grad=self.auto)
-        self.alpha = self.log_alpha.detach().exp()           # float32[1] on the device: sit_sac_target reads it there
-        self.optims = {"critic": torch.optim.Adam(self.critic.parameters(), lr=lr),
-                       "policy": torch.optim.Adam(self.policy.parameters(), lr=lr)}
-        if self.auto:
-            self.optims["alpha"] = torch.optim.Adam([self.log_alpha], lr=lr)
+        # (alpha: float32[1] on the device, where sit_sac_target reads it)
+        self._setup(torch.float32, dev, gamma=gamma, tau=tau, lr=lr, alpha=alpha,
+                    automatic_entropy_tuning=automatic_entropy_tuning, target_update_interval=target_update_interval,
+                    reward_scale=reward_scale, seed=seed)
         self._ready = False
         self._out = {}
         if target == "hip":
@@ -402,7 +396,7 @@ class SacLearner:
             self.online_weights = self.target_weights = None
             self.target_critic = copy.deepcopy(self.critic).requires_grad_(False)
         if gradient == "hip":
-            self._layers = {"policy": [_actor_layers(self.policy)], "critic": _critic_layers(self.critic)}
+            self._layers = {"policy": [_actor_layers(self.policy)], "critic": _critic_layers(self.critic), "alpha": None}
             self._blocks = {"policy": self.actor_weights, "critic": self.online_weights}
             self._params = (bind_parameters(self.actor_weights, self._layers["policy"])
                             + bind_parameters(self.online_weights, self._layers["critic"]))
@@ -428,9 +422,7 @@ class SacLearner:
         a.actor_weights, a.critic_weights = self.actor_weights.data_ptr(), self.target_weights.data_ptr()
         a.alpha = self.alpha.data_ptr()
         for name, t in (("next_state", next_state), ("reward", reward), ("mask", mask)):
-            if t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous {dt} tensor on {dev} is required")
-            setattr(a, name, t.data_ptr())
+            setattr(a, name, self._pointer(name, t))
         a.y = y.data_ptr()
         a.noise = None if noise is None else noise.data_ptr()
         if diagnostics is not None:
@@ -440,6 +432,12 @@ class SacLearner:
         with torch.cuda.device(dev):
             self.env._call("sit_sac_target", byref(a), self.env._stream())
         return y
+
+    def _pointer(self, name: str, t: torch.Tensor) -> int:
+        """The address of a kernel's input: a contiguous tensor of the env's real type on the env's device."""
+        if t.dtype != self.env.dtype or t.device != self.env.device or not t.is_contiguous():
+            raise ValueError(f"{name}: a contiguous {self.env.dtype} tensor on {self.env.device} is required")
+        return t.data_ptr()
 
     def _host_noise(self, values: np.ndarray):
         return torch.from_numpy(values.astype(np.float32)).to(self.env.device, non_blocking=True)
@@ -452,9 +450,7 @@ class SacLearner:
                                c_void_p(self.online_weights.data_ptr()), self.online_weights.numel(), self.tau,
                                self.env._stream())
         else:
-            with torch.no_grad():
-                for t, p in zip(self.target_critic.parameters(), self.critic.parameters()):
-                    t.add_(p - t, alpha=self.tau)
+            self._polyak_torch()
 
     # ---------------- one update ----------------
     def update_parameters(self, memory, batch_size: int, updates: int):
@@ -475,8 +471,8 @@ class SacLearner:
         else:
             batch = {k: v.to(torch.float32) for k, v in raw.items()}
             eps = self._host_noise(sac_noise(self.seed, np.arange(B), updates))
-            y = _torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
-                              self.alpha, self.gamma, self.reward_scale)
+            y = torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
+                             self.alpha, self.gamma, self.reward_scale)["y"]
         eps_pi = self._host_noise(policy_noise(self.seed, updates, B))
         l1, l2, lp, la, alpha = _gradient_half(self.policy, self.critic, self.optims, self.log_alpha, self.alpha,
                                                self.auto, batch, y, eps_pi)
@@ -498,12 +494,9 @@ class SacLearner:
         return _lib.SacAdam(float(g["lr"]), float(b1), float(b2), float(g["eps"]), 1.0 - b1 ** t, 1.0 - b2 ** t)
 
     def _hip_update(self, raw, B: int, updates: int):
-        dt, dev = self.env.dtype, self.env.device
+        dev = self.env.device
         y = self.td_target(raw["next_state"], raw["reward"], raw["mask"], updates)
-        state, action = raw["state"], raw["action"]
-        for name, t in (("state", state), ("action", action)):
-            if t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise ValueError(f"{name}: a contiguous {dt} tensor on {dev} is required")
+        state, action = self._pointer("state", raw["state"]), self._pointer("action", raw["action"])
         n_ws = 2 * B * _lib.SIT_SAC_WORKSPACE_ROW
         if self._ws is None or self._ws.numel() < n_ws:
             self._ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
@@ -511,7 +504,7 @@ class SacLearner:
         c.batch, c.workspace_floats, c.adam = B, self._ws.numel(), self._adam("critic")
         c.critic_weights, c.critic_m, c.critic_v = (self.online_weights.data_ptr(), self._m["critic"].data_ptr(),
                                                     self._v["critic"].data_ptr())
-        c.state, c.action, c.y = state.data_ptr(), action.data_ptr(), y.data_ptr()
+        c.state, c.action, c.y = state, action, y.data_ptr()
         c.workspace, c.results = self._ws.data_ptr(), self._results.data_ptr()
         p = _lib.SacPolicyStepArgs()
         p.batch, p.tune, p.workspace_floats = B, int(self.auto), self._ws.numel()
@@ -524,7 +517,7 @@ class SacLearner:
             p.alpha_adam = self._adam("alpha")
             p.log_alpha, p.log_alpha_m, p.log_alpha_v = (self.log_alpha.data_ptr(), self._m["alpha"].data_ptr(),
                                                          self._v["alpha"].data_ptr())
-        p.state, p.noise = state.data_ptr(), None
+        p.state, p.noise = state, None
         p.workspace, p.results = self._ws.data_ptr(), self._results.data_ptr()
         with torch.cuda.device(dev):
             stream = self.env._stream()
@@ -544,14 +537,8 @@ class SacLearner:
             return {k: copy.deepcopy(o.state_dict()) for k, o in self.optims.items()}
         out = {}
         for k, o in self.optims.items():
-            sd = copy.deepcopy(o.state_dict())
-            if k == "alpha":
-                sd["state"] = {} if self._steps[k] <= 0 else {0: {"step": torch.tensor(float(self._steps[k])),
-                                                                  "exp_avg": self._m[k].clone(),
-                                                                  "exp_avg_sq": self._v[k].clone()}}
-            else:
-                sd["state"] = moments_to_adam_state(self._m[k], self._v[k], self._layers[k], self._steps[k])
-            out[k] = sd
+            out[k] = copy.deepcopy(o.state_dict())
+            out[k]["state"] = moments_to_adam_state(self._m[k], self._v[k], self._layers[k], self._steps[k])
         return out
 
     def _load_optim_state_dicts(self, optims: dict):
@@ -561,17 +548,7 @@ class SacLearner:
             return
         for k, o in self.optims.items():
             o.load_state_dict({"state": {}, "param_groups": optims[k]["param_groups"]})    # lr, betas, eps
-            state = optims[k]["state"]
-            if k == "alpha":
-                with torch.no_grad():
-                    self._m[k].zero_()
-                    self._v[k].zero_()
-                    if state:
-                        self._m[k].copy_(state[0]["exp_avg"])
-                        self._v[k].copy_(state[0]["exp_avg_sq"])
-                self._steps[k] = int(state[0]["step"]) if state else 0
-            else:
-                self._steps[k] = adam_state_to_moments(state, self._m[k], self._v[k], self._layers[k])
+            self._steps[k] = adam_state_to_moments(optims[k]["state"], self._m[k], self._v[k], self._layers[k])
 
     # ---------------- checkpoint ----------------
     def state_dict(self) -> dict:
@@ -608,7 +585,7 @@ class SacLearner:
             pack_actor_weights(self.policy, out=self.actor_weights)
 
 
-class SacUpdateReference:
+class SacUpdateReference(_SacState):
     """``SacLearner``'s update in float64 PyTorch on the CPU: deep copies of the networks, a target
     ``QNetwork``, the TD target by the formulas of ``sac_target_reference`` and the same noise draws."""
 
@@ -618,15 +595,9 @@ class SacUpdateReference:
         self.policy = copy.deepcopy(policy).to(device="cpu", dtype=torch.float64)
         self.critic = copy.deepcopy(critic).to(device="cpu", dtype=torch.float64)
         self.target_critic = copy.deepcopy(self.critic).requires_grad_(False)
-        self.gamma, self.tau, self.reward_scale = float(gamma), float(tau), float(reward_scale)
-        self.target_update_interval, self.seed = int(target_update_interval), int(seed)
-        self.auto = bool(automatic_entropy_tuning)
-        self.log_alpha = torch.full((1,), math.log(alpha), dtype=torch.float64, requires_grad=self.auto)
-        self.alpha = self.log_alpha.detach().exp()
-        self.optims = {"critic": torch.optim.Adam(self.critic.parameters(), lr=lr),
-                       "policy": torch.optim.Adam(self.policy.parameters(), lr=lr)}
-        if self.auto:
-            self.optims["alpha"] = torch.optim.Adam([self.log_alpha], lr=lr)
+        self._setup(torch.float64, "cpu", gamma=gamma, tau=tau, lr=lr, alpha=alpha,
+                    automatic_entropy_tuning=automatic_entropy_tuning, target_update_interval=target_update_interval,
+                    reward_scale=reward_scale, seed=seed)
 
     def update_parameters(self, memory, batch_size: int, updates: int):
         B = int(batch_size)
@@ -635,17 +606,15 @@ class SacUpdateReference:
         as64 = lambda v: (v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))).to(torch.float64)  # noqa: E731
         batch = {k: as64(v) for k, v in _sample(memory, B).items()}
         eps = torch.from_numpy(sac_noise(self.seed, np.arange(B), updates))
-        y = _torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
-                          self.alpha, self.gamma, self.reward_scale)
+        y = torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
+                         self.alpha, self.gamma, self.reward_scale)["y"]
         eps_pi = torch.from_numpy(policy_noise(self.seed, updates, B))
         l1, l2, lp, la, alpha = _gradient_half(self.policy, self.critic, self.optims, self.log_alpha, self.alpha,
                                                self.auto, batch, y, eps_pi)
         if self.auto:
             self.alpha = alpha
         if updates % self.target_update_interval == 0:
-            with torch.no_grad():
-                for t, p in zip(self.target_critic.parameters(), self.critic.parameters()):
-                    t.add_(p - t, alpha=self.tau)
+            self._polyak_torch()
         return float(l1), float(l2), float(lp), float(la), float(self.alpha[0])
 
 

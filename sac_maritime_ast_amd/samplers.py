@@ -97,6 +97,19 @@ class GaussianPolicy(nn.Module):
         return action, log_pi, mu, log_sig
 
 
+def block_segments(flat, n_in: int, n_out: int, base: int = 0):
+    """The six segments of a packed (n_in -> 256 -> 256 -> n_out) block that starts at flat[base], in the
+    block's order (W1, b1, W2^T, b2, W3, b3; include/sit.h), as ``(layer 0..2, "weight" | "bias", view)``.
+    Each view has its ``nn.Linear`` parameter's shape: the second layer's is the transpose of its W2^T
+    segment.  `flat` is a 1-d torch tensor or NumPy array."""
+    H, o = _lib.SIT_ACTOR_HIDDEN, base
+    for layer, (rows, cols) in enumerate(((H, n_in), (H, H), (n_out, H))):
+        w = flat[o:o + rows * cols]
+        yield layer, "weight", w.reshape(cols, rows).T if layer == 1 else w.reshape(rows, cols)
+        yield layer, "bias", flat[o + rows * cols:o + rows * cols + rows]
+        o += rows * cols + rows
+
+
 def pack_actor_weights(policy: nn.Module, out: torch.Tensor | None = None) -> torch.Tensor | None:
     """The float32 weight block of sit_policy_actor (include/sit.h) from a GaussianPolicy whose trunk
     is the reference's default MLP (obs 10 -> 256 -> ReLU -> 256 -> ReLU -> 2; mlp.py:95-148,
@@ -123,12 +136,8 @@ def pack_actor_weights(policy: nn.Module, out: torch.Tensor | None = None) -> to
             raise ValueError(f"pack_actor_weights: out must be a contiguous float32 tensor of "
                              f"{_lib.SIT_ACTOR_WEIGHTS} elements (got {tuple(out.shape)} {out.dtype}, "
                              f"contiguous={out.is_contiguous()})")
-        o = 0
-        for t, shape in ((l1.weight, (H, _lib.SIT_OBS_DIM)), (l1.bias, (H,)), (l2.weight.t(), (H, H)), (l2.bias, (H,)),
-                         (l3.weight, (2, H)), (l3.bias, (2,))):
-            n = t.numel()
-            out[o:o + n].view(shape).copy_(t.detach())
-            o += n
+        for layer, name, seg in block_segments(out.view(-1), _lib.SIT_OBS_DIM, 2):
+            seg.copy_(getattr((l1, l2, l3)[layer], name).detach())
         return out
 
 

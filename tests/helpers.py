@@ -3,6 +3,8 @@ from __future__ import annotations
 
 import glob
 import os
+import shutil
+import subprocess
 import sys
 
 import numpy as np
@@ -43,6 +45,36 @@ SCALE = dict(north=1e4, east=1e4, yaw=np.pi, surge=10.0, sway=10.0, yaw_rate=0.1
 # d_thrust = (power - k F) / tau [N/s] (a difference of ~1e6 N terms near equilibrium)
 SCALE_SIMPL = dict(SCALE, shaft_speed=1e5, d_shaft_speed=1e4)
 OBS_SCALE = np.array([1e4, 1e4, np.pi, 1e3, 1e3, 1e3, 1e4, 1e4, np.pi, 1e3])
+
+
+SANITIZE_FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def host_compiler():
+    for cand in (os.environ.get("SIT_HOST_CXX"), "/opt/rocm/llvm/bin/clang++", "g++"):
+        if cand and (os.path.exists(cand) if os.path.sep in cand else shutil.which(cand)):
+            return cand
+    return None
+
+
+def sanitized_program_cases(name, tmp_path_factory):
+    """Compile tests/csrc/<name>.cpp (a stand-alone program over the package's headers) with the host compiler
+    under ASan + UBSan, run it as a child process and return its "case: message" lines as {case: [messages]}."""
+    import pytest
+    cxx = host_compiler()
+    if cxx is None:
+        pytest.skip(f"no host C++ compiler (ROCm's clang++ or g++) to build tests/csrc/{name}.cpp")
+    exe = str(tmp_path_factory.mktemp(name) / name)
+    subprocess.run([cxx, *SANITIZE_FLAGS, "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.join(ROOT, "sac_maritime_ast_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "csrc", name + ".cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, f"exit {r.returncode}\n{r.stderr[-4000:]}"
+    out = {}
+    for line in r.stdout.splitlines():
+        case, why = line.split(": ", 1)
+        out.setdefault(case, []).append(why)
+    return out
 
 
 def golden(name):

@@ -17,7 +17,6 @@ Bounds
   learner: 4 x the error of SacLearner(target="torch") in float32 against the float64 reference after 3
     updates (LEARNER_TORCH_ERR, measured once, below).
 """
-import copy
 import ctypes
 import functools
 import math
@@ -31,17 +30,14 @@ from helpers import OBS_SCALE
 pytestmark = pytest.mark.gpu
 
 sit = pytest.importorskip("sac_maritime_ast_amd")
-from sac_maritime_ast_amd import ReplayMemory, VecMultiShipRLEnv, _lib, make_scenario, replay_reference, sac  # noqa: E402
+from sac_maritime_ast_amd import ReplayMemory, VecMultiShipRLEnv, _lib, make_scenario, sac  # noqa: E402
 from sac_maritime_ast_amd.samplers import GaussianPolicy, PolicySampler, pack_actor_weights  # noqa: E402
+from sac_cases import (AW, CANARY, CW, DEV, GAMMA, LEARNER_KW, SEED, bits, dev, device_memory, learner_err,  # noqa: E402
+                       learner_params, networks, new_learner, records, reference_run, scaled_err)
 
-DEV = "cuda:0"
-CW, AW = _lib.SIT_CRITIC_WEIGHTS, _lib.SIT_ACTOR_WEIGHTS
 OUTPUTS = ("y", "next_action", "next_logp", "q1", "q2")
 BATCHES = (1, 7, 8, 9, 64, 67)         # one partial block, one full, one row into the second, many, 8 blocks + 3 rows
 NMAX = 67
-GAMMA, SEED = 0.99, 25450
-CANARY = -12345.5
-NP_REAL = {32: np.float32, 64: np.float64}
 TOL = 1e-5
 # Raw regime: max |float32 CPU PyTorch - float64| / max(1, |float64|) per output over the 67 fixture rows
 # (alpha 0.2, given noise): cpu_f32_error("raw") below, as test_target_raw_regime prints it.
@@ -56,41 +52,11 @@ LEARNER_TORCH_ERR = {"tuple": 1.14e-07, "params": 1.64e-07}
 LEARNER_MARGIN = 4.0
 
 
-def scaled_err(got, ref):
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max())
-
-
 @pytest.fixture(scope="module", params=[32, 64])
 def env(request):
     e = VecMultiShipRLEnv(scenario=make_scenario(64), precision=request.param, device=DEV)
     yield e
     e.close()
-
-
-@functools.lru_cache(maxsize=None)
-def records():
-    """>= 256 transition records [n, 24] of a 64-env float64 rollout in canonical order, rounded to float32."""
-    e = VecMultiShipRLEnv(scenario=make_scenario(64), precision=64, device=DEV)
-    try:
-        e.reset()
-        e.init_step()
-        out = e.rollout(3000, seed=SEED, transition_capacity=4096)
-        mem = ReplayMemory(e, 4096)
-        mem.push(out)
-        n = len(mem)
-        rec = mem.ring[:n].cpu().numpy()
-    finally:
-        e.close()
-    print("sac fixture: transition records of the 64-env rollout:", n)
-    assert 256 <= n < 4096, n
-    return rec.astype(np.float32).astype(np.float64)
-
-
-@functools.lru_cache(maxsize=None)
-def networks():
-    torch.manual_seed(11)
-    return GaussianPolicy(), sac.QNetwork()
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,11 +81,6 @@ def reference(regime, alpha, drawn):
     return sac.sac_target_reference(pack_actor_weights(pol), sac.pack_critic_weights(q), ns, reward, mask,
                                     alpha=float(np.float32(alpha)), gamma=GAMMA, noise=None if drawn else noise,
                                     seed=SEED, update=(3 << 32) | 5)
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 class Target:
@@ -254,10 +215,6 @@ def test_target_saturation_sweep(env, ls_raw):
 # ---------------------------------------------------------------------------------------------
 # kernel properties
 # ---------------------------------------------------------------------------------------------
-def bits(a):
-    return np.asarray(a).view({4: np.uint32, 8: np.uint64}[np.asarray(a).dtype.itemsize])
-
-
 @pytest.mark.parametrize("drawn", [False, True])
 def test_target_is_deterministic_and_rows_do_not_depend_on_the_batch(env, drawn):
     t = fixture_target(env, "raw", 67, 0.2, drawn)
@@ -346,65 +303,20 @@ def test_polyak_rejects_invalid_arguments(env):
 # SacLearner against sac_update_reference
 # ---------------------------------------------------------------------------------------------
 N_REC, BATCH, N_UPD = 256, 64, 3
-LEARNER_KW = dict(gamma=GAMMA, tau=0.005, lr=3e-4, alpha=0.2, automatic_entropy_tuning=True, target_update_interval=1,
-                  seed=SEED)
-
-
-def normalised_ring(precision):
-    rec = records()[:N_REC].copy()
-    rec[:, 0:10] /= OBS_SCALE
-    rec[:, 12:22] /= OBS_SCALE
-    rec = rec.astype(np.float32)
-    ring = replay_reference(N_REC, NP_REAL[precision], seed=SEED)
-    ring.push(rec.astype(NP_REAL[precision]), N_REC)
-    return ring
-
-
-def device_memory(env):
-    ring = normalised_ring(env.precision)
-    mem = ReplayMemory(env, N_REC, seed=SEED)
-    mem.ring.copy_(dev(ring.ring))
-    mem.cursor.copy_(dev(ring.cursor))
-    return mem
-
-
-def critic_params(learner):
-    """Online and target critic parameters as float64 arrays, in QNetwork order."""
-    if learner.target == "hip":
-        tq = sac.unpack_critic_weights(learner.target_weights.cpu(), sac.QNetwork())
-    else:
-        tq = learner.target_critic
-    return [p.detach().cpu().double().numpy() for m in (learner.policy, learner.critic, tq) for p in m.parameters()]
-
-
-@functools.lru_cache(maxsize=None)
-def reference_run(precision):
-    pol, q = networks()
-    ref = sac.sac_update_reference(pol, q, **LEARNER_KW)
-    ring = normalised_ring(precision)
-    tuples = [ref.update_parameters(ring, BATCH, u) for u in range(N_UPD)]
-    params = [p.detach().numpy() for m in (ref.policy, ref.critic, ref.target_critic) for p in m.parameters()]
-    return tuples, params
 
 
 def learner_run(env, target):
-    pol, q = networks()
-    learner = sac.SacLearner(env, copy.deepcopy(pol).to(DEV), critic=copy.deepcopy(q), target=target, **LEARNER_KW)
-    mem = device_memory(env)
+    learner, mem = new_learner(env, target=target), device_memory(env, N_REC)
     tuples = [learner.update_parameters(mem, BATCH, u) for u in range(N_UPD)]
     return learner, mem, tuples
 
 
-def learner_err(a_tuples, a_params, b_tuples, b_params):
-    return {"tuple": scaled_err(a_tuples, b_tuples), "params": max(scaled_err(a, b) for a, b in zip(a_params, b_params))}
-
-
 def test_learner_matches_the_float64_reference(env):
-    ref_t, ref_p = reference_run(env.precision)
+    ref_t, ref_p, _ = reference_run(env.precision, BATCH, N_UPD)
     runs = {}
     for target in ("torch", "hip"):
         learner, mem, tuples = learner_run(env, target)
-        runs[target] = (tuples, critic_params(learner))
+        runs[target] = (tuples, learner_params(learner))
         err = learner_err(tuples, runs[target][1], ref_t, ref_p)
         print(f"sac learner, f{env.precision}, target={target} against float64:", {k: f"{v:.2e}" for k, v in err.items()})
         if target == "hip":
@@ -434,9 +346,7 @@ def test_learner_state_dict_round_trip(env, target):
 
 
 def test_learner_waits_for_more_than_a_batch_and_rejects_other_architectures(env):
-    pol, q = networks()
-    learner = sac.SacLearner(env, copy.deepcopy(pol).to(DEV), critic=copy.deepcopy(q), **LEARNER_KW)
-    mem = device_memory(env)
+    learner, mem = new_learner(env), device_memory(env, N_REC)
     assert learner.update_parameters(mem, N_REC, 0) is None and int(mem.cursor[2]) == 0
     with pytest.raises(ValueError):
         sac.SacLearner(env, GaussianPolicy(hidden=(64, 64)).to(DEV), **LEARNER_KW)

@@ -37,7 +37,6 @@ csrc/sit_sac_grad.h) and of SacLearner(gradient="hip"), on float32 and float64 h
 5. Checkpoints.  6. Serving.  7. Rejections.
 """
 import copy
-import ctypes
 import functools
 import math
 
@@ -45,24 +44,16 @@ import numpy as np
 import pytest
 import torch
 
-import sac_grad_reference as R
-from helpers import OBS_SCALE
-
 pytestmark = pytest.mark.gpu
 
 sit = pytest.importorskip("sac_maritime_ast_amd")
-from sac_maritime_ast_amd import ReplayMemory, VecMultiShipRLEnv, _lib, make_scenario, replay_reference, sac  # noqa: E402
-from sac_maritime_ast_amd.samplers import GaussianPolicy, PolicySampler, pack_actor_weights  # noqa: E402
+from sac_maritime_ast_amd import ReplayMemory, VecMultiShipRLEnv, _lib, make_scenario, sac  # noqa: E402
+from sac_maritime_ast_amd.samplers import GaussianPolicy, PolicySampler  # noqa: E402
+import sac_grad_reference as R  # noqa: E402
+from sac_cases import (ADAM_EPS, BETA1, BETA2, CANARY, DEV, ROW, SEED, SEEDS, UPDATE, Steps, bits, blocks_are_the_modules,  # noqa: E402
+                       case_of, device_memory, learner_err, learner_params, new_learner, reference_run)
 
-DEV = "cuda:0"
-CW, AW, ROW = _lib.SIT_CRITIC_WEIGHTS, _lib.SIT_ACTOR_WEIGHTS, _lib.SIT_SAC_WORKSPACE_ROW
-CRITIC_SIZE = CW - 3                     # the packed network; 3 padding floats follow
-SEEDS = {1: 1, 7: 1, 8: 2, 9: 2, 64: 2, 67: 2}
-CANARY = -12345.5
 MARGIN = 4.0                             # LEARNER_MARGIN / RAW_MARGIN of tests/test_gpu_sac.py
-SEED, UPDATE = 25450, (3 << 32) | 5
-BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
-NP_REAL = {32: np.float32, 64: np.float64}
 
 
 @pytest.fixture(scope="module", params=[32, 64])
@@ -70,90 +61,6 @@ def env(request):
     e = VecMultiShipRLEnv(scenario=make_scenario(64), precision=request.param, device=DEV)
     yield e
     e.close()
-
-
-def adam_scalars(t=1, lr=R.LR):
-    return _lib.SacAdam(lr, BETA1, BETA2, ADAM_EPS, 1.0 - BETA1 ** t, 1.0 - BETA2 ** t)
-
-
-def with_tail(a, dtype):
-    """A device tensor of `a` with 8 canary elements behind it."""
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(dtype).reshape(-1)
-    return torch.cat([t, torch.full((8,), CANARY, dtype=dtype)]).to(DEV)
-
-
-class Steps:
-    """sit_sac_critic_step and sit_sac_policy_step through ctypes on buffers with 8 canary elements behind
-    each, the critic blocks' padding set to the canary as well, and zero moments."""
-
-    def __init__(self, env, case, alpha=R.ALPHA0, tune=True, drawn=False, seed=SEED, update=UPDATE):
-        self.env, self.B = env, case["B"]
-        B, dt = self.B, env.dtype
-        cw = sac.pack_critic_weights(case["critic"]).numpy().copy()
-        cw.reshape(2, CW)[:, CRITIC_SIZE:] = CANARY
-        zero_c = np.zeros(2 * CW, dtype=np.float32)
-        zero_c.reshape(2, CW)[:, CRITIC_SIZE:] = CANARY
-        self.blocks = {"critic": with_tail(cw, torch.float32), "critic_m": with_tail(zero_c, torch.float32),
-                       "critic_v": with_tail(zero_c, torch.float32),
-                       "actor": with_tail(pack_actor_weights(case["policy"]).numpy(), torch.float32),
-                       "actor_m": with_tail(np.zeros(AW, dtype=np.float32), torch.float32),
-                       "actor_v": with_tail(np.zeros(AW, dtype=np.float32), torch.float32)}
-        self.n_ws = 2 * B * ROW
-        self.ws = torch.full((self.n_ws + 8,), CANARY, dtype=torch.float32, device=DEV)
-        self.results = torch.full((5 + 8,), CANARY, dtype=torch.float32, device=DEV)
-        log_alpha = np.float32(math.log(alpha))
-        self.scalars = with_tail(np.array([np.exp(np.float64(log_alpha)), log_alpha, 0.0, 0.0]), torch.float32)
-        self.inputs = {k: with_tail(case[k], dt) for k in ("state", "action", "y", "eps")}
-        c = self.critic_args = _lib.SacCriticStepArgs()
-        c.batch, c.workspace_floats, c.adam = B, self.n_ws, adam_scalars()
-        c.critic_weights, c.critic_m, c.critic_v = (self.blocks[k].data_ptr() for k in ("critic", "critic_m", "critic_v"))
-        c.state, c.action, c.y = (self.inputs[k].data_ptr() for k in ("state", "action", "y"))
-        c.workspace, c.results = self.ws.data_ptr(), self.results.data_ptr()
-        p = self.policy_args = _lib.SacPolicyStepArgs()
-        p.batch, p.tune, p.workspace_floats, p.seed, p.update = B, int(tune), self.n_ws, seed, update
-        p.target_entropy, p.adam, p.alpha_adam = R.TARGET_ENTROPY, adam_scalars(), adam_scalars()
-        p.actor_weights, p.actor_m, p.actor_v = (self.blocks[k].data_ptr() for k in ("actor", "actor_m", "actor_v"))
-        p.critic_weights = self.blocks["critic"].data_ptr()
-        s = self.scalars.data_ptr()
-        p.alpha, p.log_alpha, p.log_alpha_m, p.log_alpha_v = s, s + 4, s + 8, s + 12
-        p.state, p.noise = self.inputs["state"].data_ptr(), None if drawn else self.inputs["eps"].data_ptr()
-        p.workspace, p.results = self.ws.data_ptr(), self.results.data_ptr()
-
-    def call(self, which):
-        fn, args = ((self.env.lib.sit_sac_critic_step, self.critic_args) if which == "critic" else
-                    (self.env.lib.sit_sac_policy_step, self.policy_args))
-        with torch.cuda.device(self.env.device):
-            return fn(self.env.handle, ctypes.byref(args), self.env._stream())
-
-    def buffers(self):
-        return {**self.blocks, "ws": self.ws, "results": self.results, "scalars": self.scalars, **self.inputs}
-
-    def check_canaries(self):
-        torch.cuda.synchronize()
-        for k, t in self.buffers().items():
-            assert torch.all(t[-8:] == CANARY), f"{k}: written past its end"
-        for k in ("critic", "critic_m", "critic_v"):
-            assert torch.all(self.blocks[k][:2 * CW].view(2, CW)[:, CRITIC_SIZE:] == CANARY), f"{k}: padding written"
-
-    def run(self, steps=("critic", "policy")):
-        for which in steps:
-            assert self.call(which) == _lib.SIT_OK, self.env.lib.sit_last_error(self.env.handle)
-        self.check_canaries()
-        return self.read()
-
-    def read(self):
-        torch.cuda.synchronize()
-        host = {k: t[:-8].cpu() for k, t in self.buffers().items()}
-        pol, q = GaussianPolicy(), sac.QNetwork()
-        views = lambda k, layers: [v.double().numpy().copy() for v in sac.block_views(host[k], layers)]  # noqa: E731
-        cl, al = sac._critic_layers(q), [sac._actor_layers(pol)]
-        g = float(np.float32(1.0 - BETA1))       # m = (1 - beta1) g in float32
-        sc = host["scalars"].double().numpy()
-        return {"critic_grads": [m / g for m in views("critic_m", cl)], "critic_params": views("critic", cl),
-                "policy_grads": [m / g for m in views("actor_m", al)], "policy_params": views("actor", al),
-                "critic_v": views("critic_v", cl), "policy_v": views("actor_v", al),
-                "results": host["results"].double().numpy(), "alpha": sc[0], "log_alpha": sc[1], "alpha_grad": sc[2] / g,
-                "raw": host}
 
 
 def adam_first_step(p0, g, lr=R.LR):
@@ -182,7 +89,7 @@ def initial_params(case):
 # ---------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def fixture_case(B):
-    case = R.make_case(B, SEEDS[B])
+    case = case_of(B)
     ref = R.autograd_steps(case, torch.float64)
     f32 = R.autograd_steps(case, torch.float32)
     return case, ref, R.errors(f32, ref)
@@ -242,7 +149,7 @@ def head_case(ls_raw, eps=None):
     """The B = 8 case with the actor's head replaced by W3 = 0 and b3 = (0, ls_raw): mu = 0 and this ls_raw
     exactly in every row, x = exp(clip(ls_raw)) eps.  The hidden layers then receive no gradient;
     dW3 = sum_b g[b] h2[b] and db3 = sum_b g[b] carry (dmu, dls)."""
-    case = dict(R.make_case(8, SEEDS[8]))
+    case = dict(case_of(8))
     case["policy"] = copy.deepcopy(case["policy"])
     with torch.no_grad():
         case["policy"].net[4].weight.zero_()
@@ -297,10 +204,6 @@ def test_saturation(env):
 # ---------------------------------------------------------------------------------------------
 # 3. determinism and bounds
 # ---------------------------------------------------------------------------------------------
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int64)
-
-
 @pytest.mark.parametrize("B", [9, 67])
 def test_two_runs_are_bit_identical(env, B):
     case = fixture_case(B)[0]
@@ -349,23 +252,12 @@ def test_invalid_arguments_launch_nothing(env):
     case = fixture_case(9)[0]
     s = Steps(env, case)
     before = {k: t.clone() for k, t in s.buffers().items()}
-    for which, args in (("critic", s.critic_args), ("policy", s.policy_args)):
-        good = {k: getattr(args, k) for k, _ in args._fields_ if k not in ("adam", "alpha_adam")}
-        block = "critic_weights" if which == "critic" else "actor_weights"
-        moment = "critic_m" if which == "critic" else "actor_v"
-        cases = [(k, None) for k in (block, moment, "state", "workspace", "results")]
-        cases += [("batch", 0), ("batch", -1), (block, good[block] + 4), (moment, good[moment] + 8),
-                  ("workspace_floats", s.n_ws - 1)]
-        if which == "policy":
-            cases += [("critic_weights", None), ("critic_weights", good["critic_weights"] + 4), ("alpha", None),
-                      ("log_alpha", None)]
-        else:
-            cases += [("action", None), ("y", None)]
-        for field, value in cases:
+    for which in ("critic", "policy"):
+        for args, field, value, good in s.invalid_arguments(which):
             setattr(args, field, value)
             assert s.call(which) == _lib.SIT_E_INVALID, (which, field)
             assert b"sac" in env.lib.sit_last_error(env.handle), (which, field)
-            setattr(args, field, good[field])
+            setattr(args, field, good)
     with torch.cuda.device(env.device):
         assert env.lib.sit_sac_critic_step(env.handle, None, env._stream()) == _lib.SIT_E_INVALID
         assert env.lib.sit_sac_policy_step(env.handle, None, env._stream()) == _lib.SIT_E_INVALID
@@ -386,95 +278,13 @@ def test_learner_rejects_other_modes_and_architectures(env):
 
 
 # ---------------------------------------------------------------------------------------------
-# 4. SacLearner against sac_update_reference (the fixture of tests/test_gpu_sac.py, re-created)
+# 4. SacLearner against sac_update_reference (the fixture of tests/sac_cases.py)
 # ---------------------------------------------------------------------------------------------
 N_REC, BATCH, N_UPD, N_MORE = 256, 64, 8, 2
-GAMMA = 0.99
-LEARNER_KW = dict(gamma=GAMMA, tau=0.005, lr=3e-4, alpha=0.2, automatic_entropy_tuning=True, target_update_interval=1,
-                  seed=SEED)
-
-
-def scaled_err(got, ref):
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max())
-
-
-@functools.lru_cache(maxsize=None)
-def records():
-    """>= 256 transition records [n, 24] of a 64-env float64 rollout in canonical order, rounded to float32."""
-    e = VecMultiShipRLEnv(scenario=make_scenario(64), precision=64, device=DEV)
-    try:
-        e.reset()
-        e.init_step()
-        out = e.rollout(3000, seed=SEED, transition_capacity=4096)
-        mem = ReplayMemory(e, 4096)
-        mem.push(out)
-        n = len(mem)
-        rec = mem.ring[:n].cpu().numpy()
-    finally:
-        e.close()
-    assert 256 <= n < 4096, n
-    return rec.astype(np.float32).astype(np.float64)
-
-
-@functools.lru_cache(maxsize=None)
-def networks():
-    torch.manual_seed(11)
-    return GaussianPolicy(), sac.QNetwork()
-
-
-def normalised_ring(precision):
-    rec = records()[:N_REC].copy()
-    rec[:, 0:10] /= OBS_SCALE
-    rec[:, 12:22] /= OBS_SCALE
-    rec = rec.astype(np.float32)
-    ring = replay_reference(N_REC, NP_REAL[precision], seed=SEED)
-    ring.push(rec.astype(NP_REAL[precision]), N_REC)
-    return ring
-
-
-def device_memory(env):
-    ring = normalised_ring(env.precision)
-    mem = ReplayMemory(env, N_REC, seed=SEED)
-    mem.ring.copy_(torch.from_numpy(np.ascontiguousarray(ring.ring)).to(DEV))
-    mem.cursor.copy_(torch.from_numpy(np.ascontiguousarray(ring.cursor)).to(DEV))
-    return mem
-
-
-def all_params(learner):
-    """Policy, online and target critic parameters as float64 arrays, in parameters() order."""
-    tq = sac.unpack_critic_weights(learner.target_weights.cpu(), sac.QNetwork())
-    return [p.detach().cpu().double().numpy() for m in (learner.policy, learner.critic, tq) for p in m.parameters()]
-
-
-@functools.lru_cache(maxsize=None)
-def reference_run(precision):
-    """The float64 reference's tuples and parameters after N_UPD and after N_UPD + N_MORE updates."""
-    pol, q = networks()
-    ref = sac.sac_update_reference(pol, q, **LEARNER_KW)
-    ring = normalised_ring(precision)
-    snap = lambda: [p.detach().numpy().copy() for m in (ref.policy, ref.critic, ref.target_critic) for p in m.parameters()]  # noqa: E731
-    tuples = [ref.update_parameters(ring, BATCH, u) for u in range(N_UPD)]
-    first = snap()
-    tuples += [ref.update_parameters(ring, BATCH, u) for u in range(N_UPD, N_UPD + N_MORE)]
-    return tuples, first, snap()
-
-
-def blocks_are_the_modules(learner):
-    return (torch.equal(learner.actor_weights, pack_actor_weights(learner.policy))
-            and torch.equal(learner.online_weights, sac.pack_critic_weights(learner.critic)))
-
-
-def new_learner(env, gradient, fresh=False):
-    pol, q = networks()
-    if fresh:
-        torch.manual_seed(99)
-        pol, q = GaussianPolicy(), sac.QNetwork()         # other initial values
-    return sac.SacLearner(env, copy.deepcopy(pol).to(DEV), critic=copy.deepcopy(q), gradient=gradient, **LEARNER_KW)
 
 
 def learner_run(env, gradient, n=N_UPD):
-    learner, mem, tuples = new_learner(env, gradient), device_memory(env), []
+    learner, mem, tuples = new_learner(env, gradient=gradient), device_memory(env, N_REC), []
     for u in range(n):
         tuples.append(learner.update_parameters(mem, BATCH, u))
         if gradient == "hip":
@@ -482,17 +292,13 @@ def learner_run(env, gradient, n=N_UPD):
     return learner, mem, tuples
 
 
-def learner_err(tuples, params, ref_tuples, ref_params):
-    return {"tuple": scaled_err(tuples, ref_tuples), "params": max(scaled_err(a, b) for a, b in zip(params, ref_params))}
-
-
 def test_learner_matches_the_float64_reference(env):
-    ref_t, ref_p, _ = reference_run(env.precision)
+    ref_t, ref_p, _ = reference_run(env.precision, BATCH, N_UPD, N_MORE)
     err = {}
     for gradient in ("torch", "hip"):
         learner, mem, tuples = learner_run(env, gradient)
         assert all(len(t) == 5 and all(isinstance(v, float) and math.isfinite(v) for v in t) for t in tuples)
-        err[gradient] = learner_err(tuples, all_params(learner), ref_t[:N_UPD], ref_p)
+        err[gradient] = learner_err(tuples, learner_params(learner), ref_t[:N_UPD], ref_p)
         print(f"sac learner, f{env.precision}, gradient={gradient}, {N_UPD} updates against float64:",
               {k: f"{v:.2e}" for k, v in err[gradient].items()})
     bad = {k: (v, err["torch"][k]) for k, v in err["hip"].items() if v > MARGIN * err["torch"][k]}
@@ -507,7 +313,7 @@ def test_hip_state_dict_round_trip_is_exact(env):
     learner, mem, _ = learner_run(env, "hip", 3)
     sd, msd = learner.state_dict(), mem.state_dict()
     want = learner.update_parameters(mem, BATCH, 3)
-    other = new_learner(env, "hip", fresh=True)
+    other = new_learner(env, fresh=True, gradient="hip")
     other.load_state_dict(sd)
     assert blocks_are_the_modules(other)
     mem.load_state_dict(msd)
@@ -524,14 +330,14 @@ def test_hip_state_dict_round_trip_is_exact(env):
 def test_checkpoints_cross_the_gradient_modes(env, first, second):
     """N_UPD updates in one mode, a checkpoint, N_MORE updates in the other: the error against the float64
     reference stays within 4 x the error of the torch mode run straight through, measured here."""
-    ref_t, _, ref_p = reference_run(env.precision)
+    ref_t, _, ref_p = reference_run(env.precision, BATCH, N_UPD, N_MORE)
     straight, smem, stuples = learner_run(env, "torch", N_UPD + N_MORE)
-    base = learner_err(stuples[N_UPD:], all_params(straight), ref_t[N_UPD:], ref_p)
+    base = learner_err(stuples[N_UPD:], learner_params(straight), ref_t[N_UPD:], ref_p)
     learner, mem, _ = learner_run(env, first)
-    other = new_learner(env, second, fresh=True)
+    other = new_learner(env, fresh=True, gradient=second)
     other.load_state_dict(learner.state_dict())
     tuples = [other.update_parameters(mem, BATCH, u) for u in range(N_UPD, N_UPD + N_MORE)]
-    err = learner_err(tuples, all_params(other), ref_t[N_UPD:], ref_p)
+    err = learner_err(tuples, learner_params(other), ref_t[N_UPD:], ref_p)
     print(f"sac checkpoint, f{env.precision}, {first} -> {second}:", {k: f"{v:.2e}" for k, v in err.items()},
           "torch straight through:", {k: f"{v:.2e}" for k, v in base.items()})
     bad = {k: (v, base[k]) for k, v in err.items() if v > MARGIN * base[k]}

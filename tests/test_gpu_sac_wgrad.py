@@ -16,25 +16,20 @@ check here is equality of bits against the plain calls from the same state, not 
 5. SacLearner(weight_gradient="mfma") against "sum": 3 updates of batch 64 from a 256-record memory, and a
    checkpoint written in either mode and continued in the other.
 
-The buffers are those of tests/test_gpu_sac_grad.py (its Steps: 8 canaries behind every buffer, the critic
-blocks' padding set to the canary), the cases tests/sac_grad_reference.make_case(B, seed).
+The buffers are those of tests/sac_cases.py (its Steps: 8 canaries behind every buffer, the critic blocks'
+padding set to the canary), the cases tests/sac_grad_reference.make_case(B, seed).
 """
-import copy
-import ctypes
-import functools
-
 import pytest
 import torch
-
-import sac_grad_reference as R
-from test_gpu_sac_grad import (BATCH, CANARY, CRITIC_SIZE, CW, DEV, LEARNER_KW, ROW, SEEDS, Steps, adam_scalars, bits,
-                               blocks_are_the_modules, device_memory, networks)
 
 pytestmark = pytest.mark.gpu
 
 sit = pytest.importorskip("sac_maritime_ast_amd")
-from sac_maritime_ast_amd import VecMultiShipRLEnv, _lib, make_scenario, sac  # noqa: E402
+from sac_maritime_ast_amd import VecMultiShipRLEnv, _lib, make_scenario  # noqa: E402
+from sac_cases import (CANARY, CRITIC_SIZE, CW, DEV, ROW, Steps, bits, blocks_are_the_modules, case_of,  # noqa: E402
+                       device_memory, new_learner)
 
+BATCH = 64
 BATCHES = [1, 2, 3, 7, 8, 9, 31, 32, 33, 64, 67, 1025, 4096]
 BLOCKS = ("critic", "critic_m", "critic_v", "actor", "actor_m", "actor_v")
 
@@ -44,29 +39,6 @@ def env(request):
     e = VecMultiShipRLEnv(scenario=make_scenario(64), precision=request.param, device=DEV)
     yield e
     e.close()
-
-
-@functools.lru_cache(maxsize=None)
-def case_of(B):
-    return R.make_case(B, SEEDS.get(B, 2))
-
-
-class PathSteps(Steps):
-    """Steps through the plain calls (tiled=False) or the _tiled ones."""
-
-    def __init__(self, env, case, tiled, **kw):
-        super().__init__(env, case, **kw)
-        self.tiled = tiled
-
-    def call(self, which):
-        fn = getattr(self.env.lib, f"sit_sac_{which}_step" + ("_tiled" if self.tiled else ""))
-        args = self.critic_args if which == "critic" else self.policy_args
-        with torch.cuda.device(self.env.device):
-            return fn(self.env.handle, ctypes.byref(args), self.env._stream())
-
-    def set_step(self, t):
-        self.critic_args.adam = adam_scalars(t)
-        self.policy_args.adam = self.policy_args.alpha_adam = adam_scalars(t)
 
 
 def assert_same_state(a, b, what):
@@ -88,8 +60,8 @@ def test_tiled_steps_are_the_plain_steps(env, B):
     case = case_of(B)
     for tune in (True, False):
         for drawn in (False, True):
-            plain = PathSteps(env, case, False, tune=tune, drawn=drawn).run()["raw"]
-            tiled = PathSteps(env, case, True, tune=tune, drawn=drawn).run()["raw"]
+            plain = Steps(env, case, tune=tune, drawn=drawn, tiled=False).run()["raw"]
+            tiled = Steps(env, case, tune=tune, drawn=drawn, tiled=True).run()["raw"]
             assert_same_state(tiled, plain, f"B={B}, tune={tune}, drawn={drawn}")
             assert torch.isfinite(tiled["results"]).all() and tiled["actor_m"].any() and tiled["critic_m"].any()
             if not tune:
@@ -104,7 +76,7 @@ def test_two_consecutive_steps(env, B):
     case = case_of(B)
     out = {}
     for tiled in (False, True):
-        s = PathSteps(env, case, tiled)
+        s = Steps(env, case, tiled=tiled)
         first = s.run()["raw"]
         s.set_step(2)
         out[tiled] = (first, s.run()["raw"])
@@ -121,7 +93,7 @@ def test_tiled_calls_keep_canaries_and_repeat(env, B):
     case = case_of(B)
     runs = []
     for _ in range(2):
-        s = PathSteps(env, case, True)
+        s = Steps(env, case, tiled=True)
         got = s.run()["raw"]                             # run() checks every canary and the padding
         assert torch.all(s.ws[s.n_ws:] == CANARY)        # the float behind row B - 1's record, where row B would be
         for k in ("critic", "critic_m", "critic_v"):
@@ -136,21 +108,10 @@ def test_tiled_calls_keep_canaries_and_repeat(env, B):
 # 4. rejections
 # ---------------------------------------------------------------------------------------------
 def test_tiled_calls_reject_what_the_plain_calls_reject(env):
-    s = PathSteps(env, case_of(9), True)
+    s = Steps(env, case_of(9), tiled=True)
     before = {k: t.clone() for k, t in s.buffers().items()}
-    for which, args in (("critic", s.critic_args), ("policy", s.policy_args)):
-        good = {k: getattr(args, k) for k, _ in args._fields_ if k not in ("adam", "alpha_adam")}
-        block = "critic_weights" if which == "critic" else "actor_weights"
-        moment = "critic_m" if which == "critic" else "actor_v"
-        cases = [(k, None) for k in (block, moment, "state", "workspace", "results")]
-        cases += [("batch", 0), ("batch", -1), (block, good[block] + 4), (moment, good[moment] + 8),
-                  ("workspace_floats", s.n_ws - 1)]
-        if which == "policy":
-            cases += [("critic_weights", None), ("critic_weights", good["critic_weights"] + 4), ("alpha", None),
-                      ("log_alpha", None)]
-        else:
-            cases += [("action", None), ("y", None)]
-        for field, value in cases:
+    for which in ("critic", "policy"):
+        for args, field, value, good in s.invalid_arguments(which):
             setattr(args, field, value)
             tiled_rc = s.call(which)
             tiled_why = env.lib.sit_last_error(env.handle)
@@ -158,7 +119,7 @@ def test_tiled_calls_reject_what_the_plain_calls_reject(env):
             assert s.call(which) == tiled_rc == _lib.SIT_E_INVALID, (which, field)
             assert env.lib.sit_last_error(env.handle) == tiled_why and b"sac" in tiled_why, (which, field)
             s.tiled = True
-            setattr(args, field, good[field])
+            setattr(args, field, good)
     with torch.cuda.device(env.device):
         assert env.lib.sit_sac_critic_step_tiled(env.handle, None, env._stream()) == _lib.SIT_E_INVALID
         assert env.lib.sit_sac_policy_step_tiled(env.handle, None, env._stream()) == _lib.SIT_E_INVALID
@@ -171,15 +132,6 @@ def test_tiled_calls_reject_what_the_plain_calls_reject(env):
 # ---------------------------------------------------------------------------------------------
 # 5. the learner
 # ---------------------------------------------------------------------------------------------
-def new_learner(env, weight_gradient, fresh=False):
-    pol, q = networks()
-    if fresh:
-        torch.manual_seed(99)
-        pol, q = type(pol)(), sac.QNetwork()             # other initial values
-    return sac.SacLearner(env, copy.deepcopy(pol).to(DEV), critic=copy.deepcopy(q), gradient="hip",
-                          weight_gradient=weight_gradient, **LEARNER_KW)
-
-
 def assert_same_learner(a, b):
     for k in ("actor_weights", "online_weights", "target_weights", "log_alpha", "alpha"):
         assert torch.equal(bits(getattr(a, k).detach()), bits(getattr(b, k).detach())), k
@@ -192,7 +144,7 @@ def assert_same_learner(a, b):
 
 
 def test_learner_modes_agree_and_share_checkpoints(env):
-    lrn = {m: new_learner(env, m) for m in ("sum", "mfma")}
+    lrn = {m: new_learner(env, gradient="hip", weight_gradient=m) for m in ("sum", "mfma")}
     mem = {m: device_memory(env) for m in lrn}
     assert lrn["mfma"].weight_gradient == "mfma" and lrn["sum"].weight_gradient == "sum"
     for u in range(3):
@@ -205,7 +157,7 @@ def test_learner_modes_agree_and_share_checkpoints(env):
     want = None
     for first, second in (("mfma", "sum"), ("sum", "mfma")):
         sd, msd = lrn[first].state_dict(), mem[first].state_dict()
-        other = new_learner(env, second, fresh=True)
+        other = new_learner(env, fresh=True, gradient="hip", weight_gradient=second)
         other.load_state_dict(sd)
         omem = device_memory(env)
         omem.load_state_dict(msd)

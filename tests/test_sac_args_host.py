@@ -4,39 +4,14 @@ tests/csrc/sac_args_main.cpp includes only sit_sac_args.h (and include/sit.h).  
 with the host compiler (-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all) and run as a
 child process; nothing is preloaded and nothing is loaded into Python.  The library calls the same
 two functions before any launch (sit_kernels.hip), so these are the messages sit_last_error gives."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from helpers import ROOT
-
-FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-
-
-def _host_compiler():
-    for cand in (os.environ.get("SIT_HOST_CXX"), "/opt/rocm/llvm/bin/clang++", "g++"):
-        if cand and (os.path.exists(cand) if os.path.sep in cand else shutil.which(cand)):
-            return cand
-    return None
+from helpers import sanitized_program_cases
 
 
 @pytest.fixture(scope="module")
 def cases(tmp_path_factory):
-    cxx = _host_compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (ROCm's clang++ or g++) to build tests/csrc/sac_args_main.cpp")
-    exe = str(tmp_path_factory.mktemp("sac_args") / "sac_args_main")
-    subprocess.run([cxx, *FLAGS, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sac_maritime_ast_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "csrc", "sac_args_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, f"exit {r.returncode}\n{r.stderr[-4000:]}"
-    out = {}
-    for line in r.stdout.splitlines():
-        name, why = line.split(": ", 1)
-        out.setdefault(name, []).append(why)
-    return out
+    return sanitized_program_cases("sac_args_main", tmp_path_factory)
 
 
 def test_acceptable_arguments(cases):
