@@ -689,7 +689,21 @@ int sit_sac_polyak(sit_handle* h, float* target, const float* online, int64_t n,
  * (v_mfma_f32_32x32x2_f32) instead of one serial sum per element.  The bits agree because the batch is the
  * MFMA's k index: the instruction is a k-ordered float32 fmaf chain with one rounding per product, taken
  * over the rows ascending from zero and never split, which is the sum above.  They are the calls for large
- * batches, where the serial sum's time grows with B per element. */
+ * batches, where the serial sum's time grows with B per element.
+ *
+ * sit_sac_target_wide, sit_sac_critic_step_wide and sit_sac_policy_step_wide take the arguments of
+ * sit_sac_target and of the two step calls, apply the same checks with the same error strings, need the same
+ * workspace, allocate nothing, never synchronise, and produce the same results as sit_sac_target and the
+ * _tiled step calls, bit for bit (the workspace records included).  Their row kernels take 32 minibatch
+ * rows per block of 256 threads instead of 8, so W2^T is streamed once per 32 rows, and run the two sums
+ * that are 95 % of a row's arithmetic as v_mfma_f32_32x32x2_f32 chains: forward layer 2,
+ * sum_k h1[b][k] W2T[k][n], as four chains per element, one per K quarter [64 q, 64 q + 64) from zero with k
+ * ascending, joined as ((q0 + q1) + (q2 + q3)) + b2; and backward layer 2, sum_n W2T[k][n] d2[b][n], as one
+ * chain per element over n = 0..255 from zero.  Those are the orders in which the other calls form these sums
+ * with fmaf, and the float32-input MFMA is a k-ordered fmaf chain with one rounding per product, so the bits
+ * agree; layers 1 and 3, d2, the Gaussian head and the loss terms are the same VALU arithmetic.  Each step
+ * call launches its wide row kernel and then the _tiled call's weight-gradient kernel.  They are the calls
+ * for large batches: with fewer than a few hundred rows there are too few blocks of 32 to fill the device. */
 #define SIT_SAC_WORKSPACE_ROW 1040
 typedef struct sit_sac_adam {
   double lr, beta1, beta2, eps;
@@ -738,6 +752,9 @@ int sit_sac_critic_step(sit_handle* h, const sit_sac_critic_step_args* a, void* 
 int sit_sac_policy_step(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
 int sit_sac_critic_step_tiled(sit_handle* h, const sit_sac_critic_step_args* a, void* stream);
 int sit_sac_policy_step_tiled(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
+int sit_sac_target_wide(sit_handle* h, const sit_sac_target_args* a, void* stream);
+int sit_sac_critic_step_wide(sit_handle* h, const sit_sac_critic_step_args* a, void* stream);
+int sit_sac_policy_step_wide(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
 
 #ifdef __cplusplus
 }

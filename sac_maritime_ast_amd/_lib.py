@@ -214,6 +214,9 @@ SIGNATURES = {
     "sit_sac_policy_step": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
     "sit_sac_critic_step_tiled": (c_int32, [c_void_p, POINTER(SacCriticStepArgs), c_void_p]),
     "sit_sac_policy_step_tiled": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
+    "sit_sac_target_wide": (c_int32, [c_void_p, POINTER(SacTargetArgs), c_void_p]),
+    "sit_sac_critic_step_wide": (c_int32, [c_void_p, POINTER(SacCriticStepArgs), c_void_p]),
+    "sit_sac_policy_step_wide": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@
 #include "sit_sac.h"
 #include "sit_sac_grad.h"
 #include "sit_sac_wgrad.h"
+#include "sit_sac_rows.h"
 
 #ifdef SIT_F32_TU
 int sit_launch_steps_f32(sit_handle* h, const void* io, void* stream);   // sit_steps_f32.hip
@@ -787,6 +788,23 @@ int sit_sac_critic_step_tiled(sit_handle* h, const sit_sac_critic_step_args* a, 
 }
 int sit_sac_policy_step_tiled(sit_handle* h, const sit_sac_policy_step_args* a, void* stream) {
   return sac_policy_step(h, a, true, stream);
+}
+
+// ---- SAC learner, the row kernels on the matrix cores (sit_sac_rows.h) -------------------------
+int sit_sac_target_wide(sit_handle* h, const sit_sac_target_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_target_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_target_wide<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+int sit_sac_critic_step_wide(sit_handle* h, const sit_sac_critic_step_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_critic_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_critic_step_wide<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+int sit_sac_policy_step_wide(sit_handle* h, const sit_sac_policy_step_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_policy_step_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_policy_step_wide<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -13,6 +13,9 @@ passes per row, weight gradients fused with Adam), which update the packed block
 networks' parameters are then views into those blocks.  ``weight_gradient="mfma"`` swaps both for their
 ``_tiled`` forms (csrc/sit_sac_wgrad.h), which form the weight gradients as 32 x 32 MFMA tiles over the
 batch instead of one serial sum per element: the same bits, and the choice for batches in the thousands.
+``row_pass="mfma"`` on top of that swaps the three row kernels for their ``_wide`` forms (csrc/sit_sac_rows.h:
+32 rows per block, both 256 x 256 products of a network pass as MFMA chains): the same bits again, and
+faster from batches of about 16 384.
 The no-gradient half is inference only and is HIP
 (csrc/sit_sac.h, include/sit.h "SAC learner"): ``sit_sac_target`` evaluates the actor at next_state
 with its log-probability, both target critics at (next_state, a') and the TD target in one kernel, and
@@ -350,6 +353,11 @@ class SacLearner(_SacState):
     over the rows in one thread.  weight_gradient="mfma": ``sit_sac_critic_step_tiled`` /
     ``sit_sac_policy_step_tiled``, the same sums as MFMA tiles with the batch as the k index; it needs
     gradient="hip", gives the same bits and keeps the same state, so checkpoints do not see it.
+    row_pass="valu" (the default): the row kernels of ``sit_sac_target`` and the step calls, 8 rows per block
+    on the VALU.  row_pass="mfma": ``sit_sac_target_wide`` / ``sit_sac_critic_step_wide`` /
+    ``sit_sac_policy_step_wide`` (csrc/sit_sac_rows.h), 32 rows per block with the two 256 x 256 products of
+    a network pass on the matrix cores; it needs weight_gradient="mfma", gives the same bits and keeps the
+    same state, so checkpoints do not see it either.  It is the mode for large batches.
 
     ``actor_weights`` is the packed actor block sit_sac_target reads, repacked in place at the end of
     every update.  A ``PolicySampler`` built on the same `policy` keeps a block of its own: call its
@@ -359,7 +367,7 @@ class SacLearner(_SacState):
     def __init__(self, env, policy: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
                  alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
                  reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None,
-                 gradient: str = "torch", weight_gradient: str = "sum"):
+                 gradient: str = "torch", weight_gradient: str = "sum", row_pass: str = "valu"):
         if target not in ("hip", "torch"):
             raise ValueError("target must be 'hip' or 'torch'")
         if gradient not in ("hip", "torch"):
@@ -370,7 +378,11 @@ class SacLearner(_SacState):
             raise ValueError("weight_gradient must be 'sum' or 'mfma'")
         if weight_gradient == "mfma" and gradient != "hip":
             raise ValueError("weight_gradient='mfma' needs gradient='hip'")
-        self.weight_gradient = weight_gradient
+        if row_pass not in ("valu", "mfma"):
+            raise ValueError("row_pass must be 'valu' or 'mfma'")
+        if row_pass == "mfma" and weight_gradient != "mfma":
+            raise ValueError("row_pass='mfma' needs weight_gradient='mfma'")
+        self.weight_gradient, self.row_pass = weight_gradient, row_pass
         self.env, self.policy, self.target, self.gradient = env, policy, target, gradient
         self.lr, self.target_entropy = float(lr), -1.0
         dev = env.device
@@ -430,7 +442,8 @@ class SacLearner(_SacState):
                 diagnostics[k] = torch.empty(B, dtype=dt, device=dev)
                 setattr(a, k, diagnostics[k].data_ptr())
         with torch.cuda.device(dev):
-            self.env._call("sit_sac_target", byref(a), self.env._stream())
+            self.env._call("sit_sac_target_wide" if self.row_pass == "mfma" else "sit_sac_target", byref(a),
+                           self.env._stream())
         return y
 
     def _pointer(self, name: str, t: torch.Tensor) -> int:
@@ -521,7 +534,7 @@ class SacLearner(_SacState):
         p.workspace, p.results = self._ws.data_ptr(), self._results.data_ptr()
         with torch.cuda.device(dev):
             stream = self.env._stream()
-            tiled = "_tiled" if self.weight_gradient == "mfma" else ""
+            tiled = "_wide" if self.row_pass == "mfma" else "_tiled" if self.weight_gradient == "mfma" else ""
             self.env._call("sit_sac_critic_step" + tiled, byref(c), stream)
             self.env._call("sit_sac_policy_step" + tiled, byref(p), stream)
             if updates % self.target_update_interval == 0:

@@ -4,6 +4,8 @@
     python3 tools/sac_cost.py [--calls 30] [--warmup 5] [out.json]
     python3 tools/sac_cost.py --gradient [--calls 30] [--warmup 5] [out.json]
     python3 tools/sac_cost.py --weight-gradient [--calls 30] [--warmup 5] [out.json]
+    python3 tools/sac_cost.py --rows [--calls 30] [--warmup 5] [out.json]
+    rocprofv3 --kernel-trace --stats ... -- python3 tools/sac_cost.py --rows --trace valu|mfma
 
 float32 handle of 64 envs, the reference's networks (actor 10-256-256-2, twin critic 11-256-256-1,
 default initialisation), a ring of 4096 synthetic normalised records.  Every figure is the median of
@@ -34,7 +36,20 @@ pass threshold; the result goes to profiles/r08_sac_cost.json.
            sit_sac_policy_step_tiled, on a learner's own blocks, interleaved call by call
   update   a whole SacLearner.update_parameters with weight_gradient="sum" and "mfma" (both gradient="hip")
 
-with, per pair, whether the tiled call's min-max range lies wholly below the plain call's."""
+with, per pair, whether the tiled call's min-max range lies wholly below the plain call's.
+
+--rows measures the wide (32 rows per block, MFMA) row kernels next to the narrow ones
+(profiles/r12_sac_rows_cost.json), at the same batch sizes from the same ring:
+
+  calls    sit_sac_target against sit_sac_target_wide, sit_sac_critic_step_tiled against
+           sit_sac_critic_step_wide and sit_sac_policy_step_tiled against sit_sac_policy_step_wide, interleaved
+           call by call (each pair differs in its row kernel only)
+  update   a whole SacLearner.update_parameters with row_pass="valu" and "mfma" (both weight_gradient="mfma")
+
+with, per pair, whether the wide call's min-max range lies wholly below the narrow call's, and the smallest
+batch from which that holds for all four.  --rows --trace MODE times nothing: it runs `warmup + calls` updates
+at B = 16384 with row_pass=MODE and exits, for a kernel trace of one mode in a run of its own (the
+row-kernel / tile-kernel split of an update: profiles/r12_sac_rows_kernel_stats.csv)."""
 import argparse
 import copy
 import json
@@ -54,12 +69,19 @@ def main():
     ap.add_argument("--gradient", action="store_true", help="measure the gradient half (r09_sac_update_cost.json)")
     ap.add_argument("--weight-gradient", action="store_true",
                     help="measure the tiled weight-gradient calls against the plain ones (r10_sac_wgrad_cost.json)")
+    ap.add_argument("--rows", action="store_true",
+                    help="measure the wide row-kernel calls against the narrow ones (r12_sac_rows_cost.json)")
+    ap.add_argument("--trace", choices=("valu", "mfma"), default=None,
+                    help="with --rows: only run updates at B = 16384 in this mode, for a profiler's kernel trace")
     ap.add_argument("out", nargs="?", default=None)
     a = ap.parse_args()
-    if a.gradient and a.weight_gradient:
-        ap.error("--gradient and --weight-gradient are separate measurements")
+    if a.trace and not a.rows:
+        ap.error("--trace goes with --rows")
+    if a.gradient + a.weight_gradient + a.rows > 1:
+        ap.error("--gradient, --weight-gradient and --rows are separate measurements")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r10_sac_wgrad_cost.json" if a.weight_gradient else
+        a.out = os.path.join(ROOT, "profiles", "r12_sac_rows_cost.json" if a.rows else
+                             "r10_sac_wgrad_cost.json" if a.weight_gradient else
                              "r09_sac_update_cost.json" if a.gradient else "r08_sac_cost.json")
     if a.calls < 20:
         ap.error("time at least 20 calls")
@@ -74,9 +96,9 @@ def main():
     torch.manual_seed(0)
     pol0, q0 = GaussianPolicy(), sac.QNetwork()
 
-    def learner(target, gradient="torch", weight_gradient="sum"):
+    def learner(target, gradient="torch", weight_gradient="sum", row_pass="valu"):
         return sac.SacLearner(env, copy.deepcopy(pol0).to(dev), critic=copy.deepcopy(q0), target=target, seed=1,
-                              gradient=gradient, weight_gradient=weight_gradient)
+                              gradient=gradient, weight_gradient=weight_gradient, row_pass=row_pass)
 
     def memory(capacity=4096):
         mem = ReplayMemory(env, capacity, seed=1)
@@ -117,6 +139,14 @@ def main():
         return finish(gradient_half(a, torch, env, _lib, learner, memory, interleaved))
     if a.weight_gradient:
         return finish(weight_gradient(a, torch, env, _lib, learner, memory, interleaved))
+    if a.rows and a.trace:
+        lrn, mem = learner("hip", "hip", "mfma", a.trace), memory(32768)
+        for u in range(a.warmup + a.calls):
+            assert lrn.update_parameters(mem, 16384, u) is not None
+        torch.cuda.synchronize()
+        return env.close()
+    if a.rows:
+        return finish(row_kernels(a, torch, env, _lib, learner, memory, interleaved))
     hip, tor = learner("hip"), learner("torch")
     res = {"what": __doc__.split("\n\n")[0], "calls": a.calls, "warmup": a.warmup,
            "device": torch.cuda.get_device_name(0), "target": {}, "polyak": {}, "update": {}}
@@ -241,6 +271,54 @@ def weight_gradient(a, torch, env, _lib, learner, memory, interleaved):
         res["batch"][str(B)] = r
     res["tiled_calls_below_plain_at_every_batch_from_1024"] = all(
         res["batch"][str(B)]["tiled_range_below_plain"][k] for B in batches if B >= 1024 for k in ("critic", "policy"))
+    return res
+
+
+def row_kernels(a, torch, env, _lib, learner, memory, interleaved):
+    """The --rows measurement (see the module docstring)."""
+    batches = (64, 256, 1024, 4096, 16384)
+    capacity = 32768
+    res = {"what": "Cost of the wide (32 rows per block, MFMA) row-kernel calls next to the narrow ones, and of a whole "
+                   "update with row_pass='mfma' next to 'valu', both weight_gradient='mfma' (GPU).", "calls": a.calls,
+           "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "ring_records": capacity, "batch": {}}
+    lrn = {m: learner("hip", "hip", "mfma", m) for m in ("valu", "mfma")}
+    mems = {k: memory(capacity) for k in lrn}
+    count = {k: 0 for k in lrn}
+    h = learner("hip", "hip", "mfma")
+    dev = env.device
+    pairs = {"target": ("sit_sac_target", "sit_sac_target_wide"),
+             "critic": ("sit_sac_critic_step_tiled", "sit_sac_critic_step_wide"),
+             "policy": ("sit_sac_policy_step_tiled", "sit_sac_policy_step_wide"), "update": ("update_valu", "update_mfma")}
+
+    def update(mode, B):
+        def fn():
+            out = lrn[mode].update_parameters(mems[mode], B, count[mode])
+            count[mode] += 1
+            assert out is not None
+        return fn
+
+    def target(mode, ns, reward, mask):
+        def fn():
+            h.row_pass = mode
+            h.td_target(ns, reward, mask, 7)
+        return fn
+    for B in batches:
+        assert len(mems["valu"]) > B
+        critic_step, policy_step = step_calls(torch, env, _lib, h, B)
+        ns = torch.randn(B, _lib.SIT_OBS_DIM, device=dev)
+        reward, mask = torch.randn(B, device=dev), torch.ones(B, device=dev)
+        r = interleaved({"sit_sac_target": target("valu", ns, reward, mask),
+                         "sit_sac_target_wide": target("mfma", ns, reward, mask),
+                         "sit_sac_critic_step_tiled": critic_step("_tiled"), "sit_sac_critic_step_wide": critic_step("_wide"),
+                         "sit_sac_policy_step_tiled": policy_step("_tiled"), "sit_sac_policy_step_wide": policy_step("_wide"),
+                         "update_valu": update("valu", B), "update_mfma": update("mfma", B)})
+        assert all(v == v for v in h._results.tolist())
+        r["wide_range_below_narrow"] = {k: r[w]["max_us"] < r[n]["min_us"] for k, (n, w) in pairs.items()}
+        r["narrow_over_wide_median"] = {k: r[n]["median_us"] / r[w]["median_us"] for k, (n, w) in pairs.items()}
+        res["batch"][str(B)] = r
+    holds = [B for B in batches if all(res["batch"][str(B)]["wide_range_below_narrow"].values())]
+    from_b = [B for B in batches if all(b in holds for b in batches if b >= B)]
+    res["smallest_batch_from_which_all_four_ranges_lie_below"] = from_b[0] if from_b else None
     return res
 
 
