@@ -756,6 +756,91 @@ int sit_sac_target_wide(sit_handle* h, const sit_sac_target_args* a, void* strea
 int sit_sac_critic_step_wide(sit_handle* h, const sit_sac_critic_step_args* a, void* stream);
 int sit_sac_policy_step_wide(sit_handle* h, const sit_sac_policy_step_args* a, void* stream);
 
+/* ---- SAC learner: many updates per call from a device clock ----------------------------
+ * The calls above take the update number and the Adam bias corrections by value, so the host forms them
+ * for every update.  sit_sac_updates enqueues n_updates whole updates whose per-update scalars come from a
+ * clock in device memory that the kernels themselves advance: the host reads nothing back, and a HIP graph
+ * of the call replays as the next n_updates updates, not as the captured ones.
+ *
+ * The clock: SIT_SAC_CLOCK_WORDS int64, caller-owned, 8-byte aligned, zero for a fresh learner.  Words 0..7
+ * are its state, and all a checkpoint needs:
+ *   {update, critic_steps, policy_steps, alpha_steps, results_written, 0, 0, 0}
+ * update is the number of the next update (the `update` of sit_sac_target / sit_sac_policy_step and the
+ * operand of the Polyak decision update % target_update_interval == 0), the three step words are the Adam
+ * steps already taken, results_written the result rows written so far.  The caller may write the state
+ * words between calls (on the stream).  The rest is opaque: two "tick" slots that hold, for one update, the
+ * three optimisers' step scalars, the update number, the Polyak flag and the results row, formed on the
+ * device.
+ *
+ * The Adam scalars of step t, a pure function of (lr, beta1, beta2, eps, t) in IEEE double without
+ * contraction, so that the host, NumPy and the device agree bit for bit:
+ *   pow_sq(beta, t):  r = 1; b = beta; n = t;  while n: { if (n & 1) r = r * b;  b = b * b;  n >>= 1 }
+ *   bias1 = 1 - pow_sq(beta1, t);  bias2 = 1 - pow_sq(beta2, t)
+ *   step_size = (float)(lr / bias1);  sqrt_bias2 = (float)sqrt(bias2)     (correctly rounded divide and sqrt)
+ *   one_minus_beta1 = (float)(1 - beta1), beta2 = (float)beta2, one_minus_beta2 = (float)(1 - beta2), eps = (float)eps
+ * At beta1 = 0.9, beta2 = 0.999 the two rounded floats equal those of bias = 1 - beta^t formed with pow (the
+ * calls above as the Python learner drives them) for every t up to 300 000 at least; for other betas
+ * pow_sq is the specification.  The `bias1`, `bias2` members of the three sit_sac_adam are ignored.
+ *
+ * sit_sac_updates: one small launch forms the first tick from the state words, then for u = 0 .. n_updates-1
+ * five launches: the target rows (sit_sac_target on slice u of next_state, reward, mask, with the target
+ * critics and y), the critic rows, the critics' Adam step, the policy rows, the actor's Adam step with the
+ * temperature step; arithmetic, noise draws and results are those of sit_sac_target, sit_sac_critic_step,
+ * sit_sac_policy_step and sit_sac_polyak called with update = clock.update and the step counts of the clock
+ * (mode: the plain, _tiled or _wide forms; the same bits).  Differences: the critics' Adam launch also
+ * applies target[e] = fma(tau, p - target[e], target[e]) to each element e it has just stepped when
+ * update % target_update_interval == 0 (padding floats are skipped: the Polyak update leaves equal values
+ * equal); the five results go to row results_written % results_capacity of `results`; and the thread that
+ * finishes the losses advances the clock: update, critic_steps, policy_steps, results_written each + 1,
+ * alpha_steps + 1 when tune != 0.  The minibatch arrays hold n_updates minibatches one after another
+ * ([n_updates][batch][...], sit_replay_sample's layout); update u reads slice u.
+ * The call validates its arguments (SIT_E_INVALID: nothing is launched), allocates nothing and never
+ * synchronises.
+ *
+ * sit_sac_adam_scalars: the device's six scalars (the order above: one_minus_beta1, beta2, one_minus_beta2,
+ * step_size, sqrt_bias2, eps) of steps t0 .. t0 + n - 1 into out[n][6]; t0 >= 1, n > 0. */
+#define SIT_SAC_CLOCK_WORDS 64
+#define SIT_SAC_UPDATES_PLAIN 0  /* sit_sac_target, sit_sac_critic_step, sit_sac_policy_step */
+#define SIT_SAC_UPDATES_TILED 1  /* sit_sac_target and the _tiled step calls */
+#define SIT_SAC_UPDATES_WIDE 2   /* the _wide calls */
+typedef struct sit_sac_updates_args {
+  int32_t mode;                /* SIT_SAC_UPDATES_* */
+  int32_t batch;               /* rows B per update, > 0 */
+  int32_t n_updates;           /* > 0 */
+  int32_t tune;                /* != 0: the temperature step */
+  uint64_t seed;               /* key of both noise draws */
+  double gamma, reward_scale, target_entropy, tau;
+  int64_t target_update_interval; /* > 0 */
+  int64_t workspace_floats;    /* elements of workspace, >= sit_sac_workspace_floats(batch) */
+  int64_t results_capacity;    /* rows of results, > 0 */
+  sit_sac_adam critic_adam;    /* bias1, bias2 are ignored in all three */
+  sit_sac_adam actor_adam;
+  sit_sac_adam alpha_adam;     /* log_alpha's (tune != 0) */
+  float* critic_weights;       /* float[2][SIT_CRITIC_WEIGHTS] (the online critics), 16-byte aligned */
+  float* critic_m;
+  float* critic_v;
+  float* actor_weights;        /* float[SIT_ACTOR_WEIGHTS], 16-byte aligned */
+  float* actor_m;
+  float* actor_v;
+  float* target_weights;       /* float[2][SIT_CRITIC_WEIGHTS] (the target critics), 16-byte aligned */
+  float* alpha;                /* float[1], device; written when tune != 0 */
+  float* log_alpha;            /* float[1] and its two moments: required when tune != 0 */
+  float* log_alpha_m;
+  float* log_alpha_v;
+  const void* state;           /* real[n_updates][B][10] */
+  const void* action;          /* real[n_updates][B] */
+  const void* reward;          /* real[n_updates][B] */
+  const void* next_state;      /* real[n_updates][B][10] */
+  const void* mask;            /* real[n_updates][B] */
+  void* y;                     /* real[B], scratch */
+  float* workspace;
+  int64_t* clock;              /* int64[SIT_SAC_CLOCK_WORDS], 8-byte aligned */
+  float* results;              /* float[results_capacity][5] */
+} sit_sac_updates_args;
+size_t sit_sac_updates_args_size(void);
+int sit_sac_updates(sit_handle* h, const sit_sac_updates_args* a, void* stream);
+int sit_sac_adam_scalars(sit_handle* h, const sit_sac_adam* o, int64_t t0, int32_t n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ SIT_CRITIC_INPUT = SIT_OBS_DIM + 1
 SIT_CRITIC_WEIGHTS = (SIT_ACTOR_HIDDEN * SIT_CRITIC_INPUT + SIT_ACTOR_HIDDEN + SIT_ACTOR_HIDDEN ** 2 + SIT_ACTOR_HIDDEN
                       + SIT_ACTOR_HIDDEN + 1 + 3) // 4 * 4
 SIT_SAC_WORKSPACE_ROW = 1040   # floats per row and network pass of the gradient half's workspace
+SIT_SAC_CLOCK_WORDS = 64       # int64 words of the device-side update clock (sit_sac_updates); 0..7 are its state
+SIT_SAC_UPDATES_PLAIN, SIT_SAC_UPDATES_TILED, SIT_SAC_UPDATES_WIDE = 0, 1, 2
 SIT_LOG_KEYS, SIT_LOG_ROWS = 27, 62
 SIT_EPISODE_ACTIONS, SIT_EPISODE_DIM = 14, 32
 INIT_FIELDS = ("north", "east", "yaw", "surge", "sway", "yaw_rate", "shaft_speed", "desired_speed",
@@ -150,6 +152,20 @@ class SacPolicyStepArgs(ctypes.Structure):
     ]
 
 
+class SacUpdatesArgs(ctypes.Structure):
+    _fields_ = [
+        ("mode", c_int32), ("batch", c_int32), ("n_updates", c_int32), ("tune", c_int32), ("seed", c_uint64),
+        ("gamma", c_double), ("reward_scale", c_double), ("target_entropy", c_double), ("tau", c_double),
+        ("target_update_interval", c_int64), ("workspace_floats", c_int64), ("results_capacity", c_int64),
+        ("critic_adam", SacAdam), ("actor_adam", SacAdam), ("alpha_adam", SacAdam),
+        ("critic_weights", c_void_p), ("critic_m", c_void_p), ("critic_v", c_void_p),
+        ("actor_weights", c_void_p), ("actor_m", c_void_p), ("actor_v", c_void_p), ("target_weights", c_void_p),
+        ("alpha", c_void_p), ("log_alpha", c_void_p), ("log_alpha_m", c_void_p), ("log_alpha_v", c_void_p),
+        ("state", c_void_p), ("action", c_void_p), ("reward", c_void_p), ("next_state", c_void_p), ("mask", c_void_p),
+        ("y", c_void_p), ("workspace", c_void_p), ("clock", c_void_p), ("results", c_void_p),
+    ]
+
+
 class SitError(RuntimeError):
     pass
 
@@ -217,6 +233,9 @@ SIGNATURES = {
     "sit_sac_target_wide": (c_int32, [c_void_p, POINTER(SacTargetArgs), c_void_p]),
     "sit_sac_critic_step_wide": (c_int32, [c_void_p, POINTER(SacCriticStepArgs), c_void_p]),
     "sit_sac_policy_step_wide": (c_int32, [c_void_p, POINTER(SacPolicyStepArgs), c_void_p]),
+    "sit_sac_updates_args_size": (c_size_t, []),
+    "sit_sac_updates": (c_int32, [c_void_p, POINTER(SacUpdatesArgs), c_void_p]),
+    "sit_sac_adam_scalars": (c_int32, [c_void_p, POINTER(SacAdam), c_int64, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -251,7 +270,8 @@ def load():
     for fn, struct in (("sit_replay_push_args_size", ReplayPushArgs), ("sit_replay_sample_args_size", ReplaySampleArgs),
                        ("sit_sac_target_args_size", SacTargetArgs),
                        ("sit_sac_critic_step_args_size", SacCriticStepArgs),
-                       ("sit_sac_policy_step_args_size", SacPolicyStepArgs)):
+                       ("sit_sac_policy_step_args_size", SacPolicyStepArgs),
+                       ("sit_sac_updates_args_size", SacUpdatesArgs)):
         if hasattr(lib, fn) and getattr(lib, fn)() != ctypes.sizeof(struct):
             raise ImportError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} vs ctypes {ctypes.sizeof(struct)} bytes")
     _lib = lib

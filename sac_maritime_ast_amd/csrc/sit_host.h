@@ -28,7 +28,7 @@ struct sit_handle {
   int lds_attr[24] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
                       -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // dynamic-LDS size per step-kernel variant
   int lds_attr_sync[12] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // k_env_steps_sync [mode][mach][lds]
-  bool lds_attr_rows[3] = {false, false, false};   // the wide SAC row kernels (sit_sac_rows.h): attribute set
+  bool lds_attr_rows[5] = {false, false, false, false, false};   // the wide SAC row kernels (sit_sac_rows.h): attribute set
   // step-kernel selection, read once at sit_create (diagnostics / A-B runs only):
   //   SIT_STEP_KERNEL=classic  k_env_steps for every mode (default: k_env_steps_sync where it applies)
   //   SIT_LDS_MAP=0|1          map read through the caches / staged in LDS for every launch

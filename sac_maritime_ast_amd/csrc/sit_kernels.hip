@@ -807,4 +807,19 @@ int sit_sac_policy_step_wide(sit_handle* h, const sit_sac_policy_step_args* a, v
   return with_real(h, [&](auto t) { return sac_launch_policy_step_wide<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
+// ---- SAC learner, many updates per call from the device clock (sit_sac_clock.h, sit_sac_rows.h) ----
+size_t sit_sac_updates_args_size(void) { return sizeof(sit_sac_updates_args); }
+
+int sit_sac_updates(sit_handle* h, const sit_sac_updates_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_updates_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return sac_launch_updates<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+int sit_sac_adam_scalars(sit_handle* h, const sit_sac_adam* o, int64_t t0, int32_t n, float* out, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = sac_adam_scalars_args_error(o, t0, n, out)) return fail(h, SIT_E_INVALID, "%s", why);
+  return sac_launch_adam_scalars(h, o, t0, n, out, (hipStream_t)stream);
+}
+
 }  // extern "C"

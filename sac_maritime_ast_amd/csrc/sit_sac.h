@@ -24,8 +24,11 @@
 #ifndef SIT_SAC_H
 #define SIT_SAC_H
 
+#include <type_traits>
+
 #include "sit_host.h"
 #include "sit_sac_args.h"
+#include "sit_sac_clock.h"
 
 namespace {
 
@@ -258,8 +261,18 @@ struct SacTarget {
   T *y, *next_action, *next_logp, *q1, *q2;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_sac_target(const SacTarget<T> a) {
+// The arguments of a clocked row kernel (sit_sac_updates): those of the kernel, whose `update` is not read, and
+// the clock's tick that holds the update number instead.  A row kernel's CLOCKED instantiation takes them; its
+// other instantiation is the kernel as it was before there was a clock, instruction for instruction.
+template <typename A>
+struct SacClocked : A {
+  const SacTick* tick;
+};
+template <typename A, bool CLOCKED>
+using SacRowArgs = std::conditional_t<CLOCKED, SacClocked<A>, A>;
+
+template <typename T, bool CLOCKED = false>
+__global__ __launch_bounds__(256) void k_sac_target(const SacRowArgs<SacTarget<T>, CLOCKED> a) {
 #pragma clang fp reassociate(off) contract(off)
   constexpr int R = kSacRows;
   __shared__ SacLds S;
@@ -272,7 +285,9 @@ __global__ __launch_bounds__(256) void k_sac_target(const SacTarget<T> a) {
   // the squashed Gaussian head and its log-probability, thread j < R = row j (rows past nrow: on zeros)
   float logp = 0.0f, act = 0.0f;
   if (j < R) {
-    const SacHead hd = sac_gaussian_head(S, j, row0 + j, j < nrow, a.noise, a.seed, a.update, kSacTag);
+    uint64_t update;
+    if constexpr (CLOCKED) update = a.tick->update; else update = a.update;
+    const SacHead hd = sac_gaussian_head(S, j, row0 + j, j < nrow, a.noise, a.seed, update, kSacTag);
     act = hd.act;
     logp = hd.logp;
     S.in[j][kActorObs] = act;

@@ -19,6 +19,11 @@
 // not depend on how blocks are scheduled.  Rows past B in the last block run on zeros with zero output
 // gradients and are neither read from nor written to global memory.
 //
+// k_sac_policy_fb and k_sac_adam have a CLOCKED instantiation for sit_sac_updates (sit_sac_clock.h): the update
+// number, the Adam scalars and the results row then come from the device clock's tick; the critics' Adam launch
+// also applies the Polyak update and the actor's finishing thread advances the clock.  The instantiations
+// without it are the kernels as they were before there was a clock.
+//
 // Included from sit_kernels.hip only (the strictly compiled translation unit).
 #ifndef SIT_SAC_GRAD_H
 #define SIT_SAC_GRAD_H
@@ -162,8 +167,9 @@ struct SacPolicyFb {
   float* ws;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_sac_policy_fb(const SacPolicyFb<T> a) {
+// (CLOCKED: sit_sac.h, SacClocked)
+template <typename T, bool CLOCKED = false>
+__global__ __launch_bounds__(256) void k_sac_policy_fb(const SacRowArgs<SacPolicyFb<T>, CLOCKED> a) {
 #pragma clang fp reassociate(off) contract(off)
   constexpr int R = kSacRows;
   __shared__ SacGradLds G;
@@ -182,7 +188,9 @@ __global__ __launch_bounds__(256) void k_sac_policy_fb(const SacPolicyFb<T> a) {
   // the squashed Gaussian head, thread j < R = row j (rows past nrow: on zeros)
   SacHead hd{};
   if (j < R) {
-    hd = sac_gaussian_head(S, j, row0 + j, j < nrow, a.noise, a.seed, a.update, kSacPolicyTag);
+    uint64_t update;
+    if constexpr (CLOCKED) update = a.tick->update; else update = a.update;
+    hd = sac_gaussian_head(S, j, row0 + j, j < nrow, a.noise, a.seed, update, kSacPolicyTag);
     S.in[j][kActorObs] = hd.act;
   }
   __syncthreads();
@@ -243,9 +251,7 @@ __global__ __launch_bounds__(256) void k_sac_policy_fb(const SacPolicyFb<T> a) {
   sac_store_fields(rec, nrow, kWsD1, S.part[1], kWsD2, S.part[0]);
 }
 
-struct SacAdamScalars {
-  float one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bias2, eps;
-};
+// (SacAdamScalars: sit_sac_clock.h)
 
 __device__ __forceinline__ void sac_adam_apply(const SacAdamScalars& o, float g, float* p, float* m, float* v) {
 #pragma clang fp reassociate(off) contract(off)
@@ -292,11 +298,53 @@ __device__ __forceinline__ void sac_finish_losses(const SacAdam& a, int c, doubl
   a.results[4] = *a.alpha;
 }
 
+// What an Adam kernel's CLOCKED instantiation (sit_sac_updates) takes besides SacAdam, whose o, oa and results
+// it replaces from the tick of slot `slot`: the critics' launch the target block of the Polyak update, the
+// actor's launch the hyper-parameters from which its finishing thread forms the next update's tick in the
+// other slot.  The other instantiation is the kernel as it was before there was a clock.
+struct SacAdamClock {
+  int64_t* clock;
+  int slot;
+  float* target;
+  float tau;
+  SacClockHyper hy;
+};
+struct SacAdamClocked : SacAdam {
+  SacAdamClock k;
+};
+template <bool CLOCKED>
+using SacAdamArgs = std::conditional_t<CLOCKED, SacAdamClocked, SacAdam>;
+
+// SacAdam as the finishing thread of a clocked launch sees it: the step's scalars and the results row from the tick
+template <bool TEMPERATURE>
+__device__ __forceinline__ SacAdam sac_adam_from_tick(const SacAdamClocked& a) {
+  const SacTick* t = sac_clock_tick(a.k.clock, a.k.slot);
+  SacAdam b = a;
+  b.o = t->o[TEMPERATURE ? kClockPolicy : kClockCritic];
+  if (TEMPERATURE) b.oa = t->o[kClockAlpha];
+  b.results = a.results + 5 * t->results_row;
+  return b;
+}
+
+// The Adam step of one element in a clocked launch, with the tick's scalars; the critics' launch then applies
+// the Polyak update to the element when the tick says so: k_sac_polyak's arithmetic on the values k_sac_polyak
+// would read, since nothing writes the online critics between the two.
+template <bool TEMPERATURE>
+__device__ __forceinline__ void sac_adam_apply_clocked(const SacAdamClocked& a, const SacTick* t, float g, size_t e) {
+#pragma clang fp reassociate(off) contract(off)
+  sac_adam_apply(t->o[TEMPERATURE ? kClockPolicy : kClockCritic], g, a.p + e, a.m + e, a.v + e);
+  if (!TEMPERATURE && t->polyak) {
+    float* target = a.k.target + e;
+    *target = __builtin_fmaf(a.k.tau, a.p[e] - *target, *target);
+  }
+}
+
 // NETS networks of SacNet<IN, NOUT>, STRIDE floats apart (the records of network c are pass c).
 // TEMPERATURE: the actor's launch (results[2..4] and the temperature step) instead of the critics'
-// (results[0..1]).
-template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE>
-__global__ __launch_bounds__(256) void k_sac_adam(const SacAdam a) {
+// (results[0..1]).  CLOCKED: scalars and results row from the clock's tick; the critics' launch also applies
+// the Polyak update, and the actor's finishing thread advances the clock.
+template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE, bool CLOCKED = false>
+__global__ __launch_bounds__(256) void k_sac_adam(const SacAdamArgs<CLOCKED> a) {
 #pragma clang fp reassociate(off) contract(off)
   static_assert(!TEMPERATURE || NETS == 1, "the temperature step belongs to the actor's launch");
   constexpr unsigned kBlocks = (NETS * STRIDE + 255) / 256;
@@ -312,8 +360,10 @@ __global__ __launch_bounds__(256) void k_sac_adam(const SacAdam a) {
         sum += (double)g[(size_t)b * kWsRow + 2];
         if (TEMPERATURE) ent += (double)g[(size_t)b * kWsRow + 3] + (double)a.target_entropy;
       }
-      sac_finish_losses<TEMPERATURE>(a, c, sum, ent);
+      if constexpr (CLOCKED) sac_finish_losses<TEMPERATURE>(sac_adam_from_tick<TEMPERATURE>(a), c, sum, ent);
+      else sac_finish_losses<TEMPERATURE>(a, c, sum, ent);
     }
+    if constexpr (CLOCKED && TEMPERATURE) sac_clock_advance(a.k.clock, a.k.hy, a.k.slot ^ 1);
     return;
   }
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -338,7 +388,8 @@ __global__ __launch_bounds__(256) void k_sac_adam(const SacAdam a) {
     const int at = row_at >= 0 ? row_at : col_at;
     for (int b = 0; b < B; ++b) g += rec[(size_t)b * kWsRow + at];
   }
-  sac_adam_apply(a.o, g, a.p + e, a.m + e, a.v + e);
+  if constexpr (CLOCKED) sac_adam_apply_clocked<TEMPERATURE>(a, sac_clock_tick(a.k.clock, a.k.slot), g, (size_t)e);
+  else sac_adam_apply(a.o, g, a.p + e, a.m + e, a.v + e);
 }
 
 inline SacAdamScalars sac_adam_scalars(const sit_sac_adam& o) {
@@ -361,6 +412,22 @@ struct SacAdamLaunch {
 
 inline int sac_launch_adam(sit_handle* h, const SacAdamLaunch& k, const SacAdam& a, hipStream_t stream) {
   hipLaunchKernelGGL(k.kernel, dim3(k.blocks), dim3(k.threads), 0, stream, a);
+  HIP_TRY(h, hipGetLastError());
+  return SIT_OK;
+}
+
+// the same for the clocked forms (sit_sac_updates)
+struct SacAdamClockLaunch {
+  void (*kernel)(const SacAdamClocked);
+  unsigned blocks, threads;
+};
+
+inline int sac_launch_adam_clocked(sit_handle* h, const SacAdamClockLaunch& k, const SacAdam& a, const SacAdamClock& c,
+                                   hipStream_t stream) {
+  SacAdamClocked ac{};
+  static_cast<SacAdam&>(ac) = a;
+  ac.k = c;
+  hipLaunchKernelGGL(k.kernel, dim3(k.blocks), dim3(k.threads), 0, stream, ac);
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;
 }

@@ -342,8 +342,8 @@ __device__ __forceinline__ void sac_rows_store_x(float* rec, int nrow, const Sac
   extern __shared__ __align__(16) unsigned char sac_rows_smem[];         \
   SacRowsLds& S = *reinterpret_cast<SacRowsLds*>(sac_rows_smem)
 
-template <typename T>
-__global__ __launch_bounds__(256, 2) void k_sac_target_wide(const SacTarget<T> a) {
+template <typename T, bool CLOCKED = false>
+__global__ __launch_bounds__(256, 2) void k_sac_target_wide(const SacRowArgs<SacTarget<T>, CLOCKED> a) {
 #pragma clang fp reassociate(off) contract(off)
   constexpr int R = kRwRows;
   SAC_ROWS_LDS(S);
@@ -355,7 +355,9 @@ __global__ __launch_bounds__(256, 2) void k_sac_target_wide(const SacTarget<T> a
   sac_rows_mlp<kActorObs, 2>(a.actor, S);
   float logp = 0.0f, act = 0.0f;
   if (j < R) {
-    const SacHead hd = sac_rows_head(S, j, row0 + j, j < nrow, a.noise, a.seed, a.update, kSacTag);
+    uint64_t update;
+    if constexpr (CLOCKED) update = a.tick->update; else update = a.update;
+    const SacHead hd = sac_rows_head(S, j, row0 + j, j < nrow, a.noise, a.seed, update, kSacTag);
     act = hd.act;
     logp = hd.logp;
     S.in[j][kActorObs] = act;
@@ -413,8 +415,8 @@ __global__ __launch_bounds__(256, 2) void k_sac_critic_fb_wide(const SacCriticFb
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256, 2) void k_sac_policy_fb_wide(const SacPolicyFb<T> a) {
+template <typename T, bool CLOCKED = false>
+__global__ __launch_bounds__(256, 2) void k_sac_policy_fb_wide(const SacRowArgs<SacPolicyFb<T>, CLOCKED> a) {
 #pragma clang fp reassociate(off) contract(off)
   constexpr int R = kRwRows;
   SAC_ROWS_LDS(S);
@@ -436,7 +438,9 @@ __global__ __launch_bounds__(256, 2) void k_sac_policy_fb_wide(const SacPolicyFb
   // the squashed Gaussian head, thread j < R = row j (rows past nrow: on zeros)
   SacHead hd{};
   if (j < R) {
-    hd = sac_rows_head(S, j, row0 + j, j < nrow, a.noise, a.seed, a.update, kSacPolicyTag);
+    uint64_t update;
+    if constexpr (CLOCKED) update = a.tick->update; else update = a.update;
+    hd = sac_rows_head(S, j, row0 + j, j < nrow, a.noise, a.seed, update, kSacPolicyTag);
     S.in[j][kActorObs] = hd.act;
   }
   __syncthreads();
@@ -591,6 +595,133 @@ int sac_launch_policy_step_wide(sit_handle* h, const sit_sac_policy_step_args* s
     a.oa = sac_adam_scalars(s->alpha_adam);
   }
   return sac_launch_adam(h, sac_adam_launch<kActorObs, 2, 1, SIT_ACTOR_WEIGHTS, true>(true), a, stream);
+}
+
+// ---- many updates per call from the device clock (include/sit.h: sit_sac_updates; sit_sac_clock.h) ----------
+//
+// One k_sac_clock_begin forms tick slot 0 from the clock's state words; update u of the call then reads slot
+// u & 1 in five launches: target rows, critic rows, critics' Adam (+ Polyak), policy rows, actor's Adam (+ the
+// temperature step, the clock's advance and the next tick in slot (u + 1) & 1).  The slot is a by-value
+// argument and the launches of a stream run in order, so a tick is complete before anything reads it and is
+// not written while anything may.  The wide row kernels' clocked instantiations are kernels of their own and
+// take slots 3, 4 of the handle's lds_attr_rows (sac_rows_launch).
+
+__global__ void k_sac_clock_begin(int64_t* clock, const SacClockHyper hy) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) sac_clock_form_tick(clock, hy, 0);
+}
+
+// the scalars of steps t0 .. t0 + n - 1 as the device forms them (the specification's test hook)
+__global__ __launch_bounds__(256) void k_sac_adam_scalars(const sit_sac_adam o, int64_t t0, int n, float* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const SacAdamScalars s = sac_clock_scalars(o, t0 + i);
+  float* p = out + (size_t)i * 6;
+  p[0] = s.one_minus_beta1; p[1] = s.beta2; p[2] = s.one_minus_beta2;
+  p[3] = s.step_size; p[4] = s.sqrt_bias2; p[5] = s.eps;
+}
+
+inline int sac_launch_adam_scalars(sit_handle* h, const sit_sac_adam* o, int64_t t0, int32_t n, float* out,
+                                   hipStream_t stream) {
+  hipLaunchKernelGGL(k_sac_adam_scalars, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *o, t0, (int)n, out);
+  HIP_TRY(h, hipGetLastError());
+  return SIT_OK;
+}
+
+template <typename T>
+int sac_launch_updates(sit_handle* h, const sit_sac_updates_args* s, hipStream_t stream) {
+  const bool tiled = s->mode != SIT_SAC_UPDATES_PLAIN, wide = s->mode == SIT_SAC_UPDATES_WIDE;
+  const int B = s->batch;
+  const unsigned narrow_blocks = (unsigned)((B + kSacRows - 1) / kSacRows);
+  SacClockHyper hy{};
+  hy.adam[kClockCritic] = s->critic_adam;
+  hy.adam[kClockPolicy] = s->actor_adam;
+  hy.adam[kClockAlpha] = s->tune ? s->alpha_adam : s->actor_adam;   // (untuned: formed, never used)
+  hy.target_update_interval = s->target_update_interval;
+  hy.results_capacity = s->results_capacity;
+  hy.tune = s->tune != 0;
+  hipLaunchKernelGGL(k_sac_clock_begin, dim3(1), dim3(64), 0, stream, s->clock, hy);
+  HIP_TRY(h, hipGetLastError());
+
+  const SacAdamClockLaunch critic_adam = sac_adam_clocked_launch<kSacIn, 1, 2, SIT_CRITIC_WEIGHTS, false>(tiled);
+  const SacAdamClockLaunch actor_adam = sac_adam_clocked_launch<kActorObs, 2, 1, SIT_ACTOR_WEIGHTS, true>(tiled);
+  for (int u = 0; u < s->n_updates; ++u) {
+    const size_t row0 = (size_t)u * (size_t)B;
+    const SacTick* tick = sac_clock_tick(s->clock, u & 1);
+    const T* state = (const T*)s->state + row0 * kActorObs;
+
+    SacClocked<SacTarget<T>> t{};
+    t.tick = tick;
+    t.batch = B;
+    t.seed = s->seed;
+    t.gamma = (T)s->gamma;
+    t.reward_scale = (T)s->reward_scale;
+    t.actor = s->actor_weights;
+    t.critic = s->target_weights;
+    t.alpha = s->alpha;
+    t.next_state = (const T*)s->next_state + row0 * kActorObs;
+    t.reward = (const T*)s->reward + row0;
+    t.mask = (const T*)s->mask + row0;
+    t.y = (T*)s->y;
+    if (wide) {
+      if (int rc = sac_rows_launch(h, 3, k_sac_target_wide<T, true>, B, t, stream)) return rc;
+    } else {
+      hipLaunchKernelGGL((k_sac_target<T, true>), dim3(narrow_blocks), dim3(256), 0, stream, t);
+      HIP_TRY(h, hipGetLastError());
+    }
+
+    SacCriticFb<T> cf{};
+    cf.batch = B;
+    cf.critic = s->critic_weights;
+    cf.state = state;
+    cf.action = (const T*)s->action + row0;
+    cf.y = (const T*)s->y;
+    cf.ws = s->workspace;
+    if (wide) {
+      if (int rc = sac_rows_launch(h, 1, k_sac_critic_fb_wide<T>, B, cf, stream)) return rc;
+    } else {
+      hipLaunchKernelGGL(k_sac_critic_fb<T>, dim3(narrow_blocks), dim3(256), 0, stream, cf);
+      HIP_TRY(h, hipGetLastError());
+    }
+    SacAdamClock k{};
+    k.clock = s->clock;
+    k.slot = u & 1;
+    k.target = s->target_weights;
+    k.tau = (float)s->tau;
+    k.hy = hy;
+    SacAdam ca{};
+    ca.batch = B;
+    ca.p = s->critic_weights; ca.m = s->critic_m; ca.v = s->critic_v;
+    ca.ws = s->workspace;
+    ca.results = s->results;
+    if (int rc = sac_launch_adam_clocked(h, critic_adam, ca, k, stream)) return rc;
+
+    SacClocked<SacPolicyFb<T>> pf{};
+    pf.tick = tick;
+    pf.batch = B;
+    pf.seed = s->seed;
+    pf.actor = s->actor_weights;
+    pf.critic = s->critic_weights;
+    pf.alpha = s->alpha;
+    pf.state = state;
+    pf.ws = s->workspace;
+    if (wide) {
+      if (int rc = sac_rows_launch(h, 4, k_sac_policy_fb_wide<T, true>, B, pf, stream)) return rc;
+    } else {
+      hipLaunchKernelGGL((k_sac_policy_fb<T, true>), dim3(narrow_blocks), dim3(256), 0, stream, pf);
+      HIP_TRY(h, hipGetLastError());
+    }
+    SacAdam pa{};
+    pa.batch = B;
+    pa.p = s->actor_weights; pa.m = s->actor_m; pa.v = s->actor_v;
+    pa.ws = s->workspace;
+    pa.results = s->results;
+    pa.tune = s->tune != 0;
+    pa.target_entropy = (float)s->target_entropy;
+    pa.alpha = s->alpha;
+    if (pa.tune) { pa.log_alpha = s->log_alpha; pa.log_alpha_m = s->log_alpha_m; pa.log_alpha_v = s->log_alpha_v; }
+    if (int rc = sac_launch_adam_clocked(h, actor_adam, pa, k, stream)) return rc;
+  }
+  return SIT_OK;
 }
 
 }  // namespace

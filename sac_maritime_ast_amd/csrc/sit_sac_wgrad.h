@@ -181,8 +181,9 @@ __device__ __forceinline__ void sac_wgrad_loss_sums(const float* g, int batch, f
 
 // NETS networks of SacNet<IN, NOUT>, STRIDE floats apart: blocks of one wave, kWgTiles tile blocks per
 // network, then the loss blocks (one per network; TEMPERATURE: one, which also takes the temperature step).
-template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE>
-__global__ __launch_bounds__(64) void k_sac_wgrad_adam(const SacAdam a) {
+// CLOCKED: as in k_sac_adam (sit_sac_grad.h).
+template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE, bool CLOCKED = false>
+__global__ __launch_bounds__(64) void k_sac_wgrad_adam(const SacAdamArgs<CLOCKED> a) {
 #pragma clang fp reassociate(off) contract(off)
   static_assert(!TEMPERATURE || NETS == 1, "the temperature step belongs to the actor's launch");
   const int B = a.batch;
@@ -191,7 +192,14 @@ __global__ __launch_bounds__(64) void k_sac_wgrad_adam(const SacAdam a) {
     const int c = blk - NETS * kWgTiles;
     double sum = 0.0, ent = 0.0;
     sac_wgrad_loss_sums<TEMPERATURE>(a.ws + (size_t)c * (size_t)B * kWsRow + kWsG, B, a.target_entropy, sum, ent);
-    if (threadIdx.x == 0) sac_finish_losses<TEMPERATURE>(a, c, sum, ent);
+    if constexpr (CLOCKED) {
+      if (threadIdx.x == 0) {
+        sac_finish_losses<TEMPERATURE>(sac_adam_from_tick<TEMPERATURE>(a), c, sum, ent);
+        if (TEMPERATURE) sac_clock_advance(a.k.clock, a.k.hy, a.k.slot ^ 1);
+      }
+    } else {
+      if (threadIdx.x == 0) sac_finish_losses<TEMPERATURE>(a, c, sum, ent);
+    }
     return;
   }
   const int c = blk / kWgTiles;
@@ -245,7 +253,8 @@ __global__ __launch_bounds__(64) void k_sac_wgrad_adam(const SacAdam a) {
     const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
     if (row < d.rows) {
       const size_t e = corner + (size_t)row * (size_t)d.stride;
-      sac_adam_apply(a.o, acc[r], a.p + e, a.m + e, a.v + e);
+      if constexpr (CLOCKED) sac_adam_apply_clocked<TEMPERATURE>(a, sac_clock_tick(a.k.clock, a.k.slot), acc[r], e);
+      else sac_adam_apply(a.o, acc[r], a.p + e, a.m + e, a.v + e);
     }
   }
 }
@@ -255,6 +264,12 @@ template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE>
 inline SacAdamLaunch sac_adam_launch(bool tiled) {
   if (!tiled) return {k_sac_adam<IN, NOUT, NETS, STRIDE, TEMPERATURE>, (NETS * STRIDE + 255) / 256 + 1, 256};
   return {k_sac_wgrad_adam<IN, NOUT, NETS, STRIDE, TEMPERATURE>, NETS * kWgTiles + NETS, 64};
+}
+
+template <int IN, int NOUT, int NETS, int STRIDE, bool TEMPERATURE>
+inline SacAdamClockLaunch sac_adam_clocked_launch(bool tiled) {
+  if (!tiled) return {k_sac_adam<IN, NOUT, NETS, STRIDE, TEMPERATURE, true>, (NETS * STRIDE + 255) / 256 + 1, 256};
+  return {k_sac_wgrad_adam<IN, NOUT, NETS, STRIDE, TEMPERATURE, true>, NETS * kWgTiles + NETS, 64};
 }
 
 }  // namespace

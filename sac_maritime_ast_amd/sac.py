@@ -26,9 +26,16 @@ architectures ``pack_actor_weights`` / ``pack_critic_weights`` decline).
 ``sac_target_reference`` is the executable specification of ``sit_sac_target`` in float64 NumPy,
 noise draw included; ``sac_update_reference`` is a whole update in float64 PyTorch on the CPU.
 
-Not included: graph capture of an update, a device-side results queue (each update reads its five
-results on the host), HIP gradients for other architectures, prioritised replay, n-step returns,
-observation normalisation, multi-rank learners.
+``update_many`` (gradient="hip") runs n updates in one call, ``sit_sac_updates``: the update number, the Adam
+step counts and the results row come from a clock in device memory that the kernels advance themselves
+(csrc/sit_sac_clock.h), so nothing is read back, a HIP graph of the call replays as the next n updates, and
+with ``PolicySampler.share_weights`` a whole "rollout, push, n updates" iteration is one graph.  The bits are
+those of the same number of ``update_parameters`` calls; ``adam_scalars_reference`` is the specification of the
+clock's Adam scalars.
+
+Not included: HIP gradients for other architectures, prioritised replay, n-step returns,
+observation normalisation, multi-rank learners, hyper-parameter schedules inside a graph, a device-side gate
+on len(memory).
 """
 from __future__ import annotations
 
@@ -212,6 +219,34 @@ def policy_noise(seed: int, update: int, batch: int) -> np.ndarray:
     return sac_noise(seed, np.arange(batch), update, POLICY_NOISE_TAG)
 
 
+def adam_scalars_reference(lr: float, beta1: float, beta2: float, eps: float, t) -> np.ndarray:
+    """The six float32 scalars of Adam step(s) `t` >= 1 as sit_sac_updates' clock forms them (include/sit.h):
+    [..., 6] = one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bias2, eps.  beta^t is a product by
+    repeated squaring in IEEE double, then step_size = float32(lr / (1 - beta1^t)) and sqrt_bias2 =
+    float32(sqrt(1 - beta2^t)); `t` may be an integer or an integer array."""
+    t = np.asarray(t, dtype=np.int64)
+    if (t < 1).any():
+        raise ValueError("adam_scalars_reference: t must be at least 1")
+
+    def pow_sq(beta):
+        r, b, n = np.ones(t.shape, dtype=np.float64), np.full(t.shape, beta, dtype=np.float64), t.copy()
+        with np.errstate(under="ignore"):
+            while n.any():
+                r = np.where(n & 1, r * b, r)
+                b = b * b
+                n >>= 1
+        return r
+    bias1, bias2 = 1.0 - pow_sq(float(beta1)), 1.0 - pow_sq(float(beta2))
+    out = np.empty(t.shape + (6,), dtype=np.float32)
+    out[..., 0] = np.float32(1.0 - float(beta1))
+    out[..., 1] = np.float32(float(beta2))
+    out[..., 2] = np.float32(1.0 - float(beta2))
+    out[..., 3] = (float(lr) / bias1).astype(np.float32)
+    out[..., 4] = np.sqrt(bias2).astype(np.float32)
+    out[..., 5] = np.float32(float(eps))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # the specification of sit_sac_target
 # ---------------------------------------------------------------------------------------------
@@ -362,12 +397,21 @@ class SacLearner(_SacState):
     ``actor_weights`` is the packed actor block sit_sac_target reads, repacked in place at the end of
     every update.  A ``PolicySampler`` built on the same `policy` keeps a block of its own: call its
     ``refresh_weights()`` after an update (its ``launch()`` does so by itself when the parameters
-    changed, except inside a HIP-graph replay)."""
+    changed, except inside a HIP-graph replay); with gradient="hip" its ``share_weights(learner.actor_weights)``
+    makes it serve from this block instead.
+
+    ``update_many(memory, batch_size, n_updates)`` (gradient="hip"): n updates in one ``sit_sac_updates`` call
+    driven by ``clock``, the int64 device clock (words 0..4: update, critic_steps, policy_steps, alpha_steps,
+    results_written); the five results of each go to a ring of `results_capacity` rows that ``results()``
+    reads.  ``update_parameters``, ``update_many``, graph replays, ``state_dict`` and ``load_state_dict`` may be
+    mixed freely: the clock's step words are the master copy once ``update_many`` has run, and the host's
+    counts are reconciled with them (one read) where they are needed."""
 
     def __init__(self, env, policy: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
                  alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
                  reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None,
-                 gradient: str = "torch", weight_gradient: str = "sum", row_pass: str = "valu"):
+                 gradient: str = "torch", weight_gradient: str = "sum", row_pass: str = "valu",
+                 results_capacity: int = 1024):
         if target not in ("hip", "torch"):
             raise ValueError("target must be 'hip' or 'torch'")
         if gradient not in ("hip", "torch"):
@@ -418,6 +462,16 @@ class SacLearner(_SacState):
             self._steps = {k: 0 for k in self.optims}
             self._results = torch.zeros(5, dtype=torch.float32, device=dev)
             self._ws = None
+            # update_many: the device clock, the results ring and the minibatch buffers per (batch, n_updates)
+            if int(results_capacity) <= 0:
+                raise ValueError("results_capacity must be positive")
+            self.clock = torch.zeros(_lib.SIT_SAC_CLOCK_WORDS, dtype=torch.int64, device=dev)
+            self._ring = torch.zeros((int(results_capacity), 5), dtype=torch.float32, device=dev)
+            self._many = {}
+            self._next_update = 0         # what the clock's update word starts from when update_many first runs
+            self._clocked = False         # update_many has run: the clock's step words are the master copy
+            self._clock_dirty = False     # clocked work since the host's counts were last reconciled
+            self._captured = False        # an update_many was captured: replays advance the clock unseen
 
     # ---------------- the no-gradient half ----------------
     def td_target(self, next_state, reward, mask, update: int, noise=None, diagnostics: dict | None = None):
@@ -508,6 +562,7 @@ class SacLearner(_SacState):
 
     def _hip_update(self, raw, B: int, updates: int):
         dev = self.env.device
+        self._reconcile()
         y = self.td_target(raw["next_state"], raw["reward"], raw["mask"], updates)
         state, action = self._pointer("state", raw["state"]), self._pointer("action", raw["action"])
         n_ws = 2 * B * _lib.SIT_SAC_WORKSPACE_ROW
@@ -541,7 +596,108 @@ class SacLearner(_SacState):
                 self.env._call("sit_sac_polyak", c_void_p(self.target_weights.data_ptr()),
                                c_void_p(self.online_weights.data_ptr()), self.online_weights.numel(), self.tau, stream)
         touch_parameters(self._params + ([self.log_alpha] if self.auto else []))
+        self._next_update = int(updates) + 1
+        if self._clocked:
+            self._write_clock()
         return tuple(self._results.tolist())
+
+    # ---------------- many updates per call, gradient="hip" ----------------
+    def _write_clock(self):
+        """The host's step counts and next update number into the clock's state words, on the stream (fills)."""
+        for word, value in ((0, self._next_update), (1, self._steps["critic"]), (2, self._steps["policy"]),
+                            (3, self._steps.get("alpha", 0))):
+            self.clock[word:word + 1].fill_(int(value))
+
+    def _reconcile(self):
+        """The host's step counts from the clock: one read when clocked work happened since the last one."""
+        if self.gradient != "hip" or not self._clock_dirty:
+            return
+        c = self.clock[:8].tolist()
+        self._next_update = c[0]
+        self._steps["critic"], self._steps["policy"] = c[1], c[2]
+        if "alpha" in self._steps:
+            self._steps["alpha"] = c[3]
+        self._clock_dirty = self._captured       # a captured graph may advance the clock again at any time
+
+    def _clocked_adam(self, key: str) -> _lib.SacAdam:
+        g = self.optims[key].param_groups[0]
+        b1, b2 = g["betas"]
+        return _lib.SacAdam(float(g["lr"]), float(b1), float(b2), float(g["eps"]), 1.0, 1.0)
+
+    def update_many(self, memory, batch_size: int, n_updates: int, first_update: int | None = None) -> None:
+        """`n_updates` SAC updates from `n_updates` fresh minibatches of `memory` in one ``sit_sac_updates`` call;
+        nothing is read back (``results()`` reads the losses).  first_update: the update number of the first
+        one (the `updates` of ``update_parameters``); None continues from the clock.  Raises ValueError while
+        len(memory) <= batch_size, and touches nothing then.  After one eager call with the same (batch_size,
+        n_updates) the call can be captured in a HIP graph (one stream; first_update must be None there): a
+        replay runs the next `n_updates` updates."""
+        if self.gradient != "hip":
+            raise ValueError("update_many needs gradient='hip'")
+        B, U = int(batch_size), int(n_updates)
+        if B <= 0 or U <= 0:
+            raise ValueError("batch_size and n_updates must be positive")
+        dev, key = self.env.device, (B, U)
+        n_ws = 2 * B * _lib.SIT_SAC_WORKSPACE_ROW
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            if first_update is not None:
+                raise ValueError("update_many: first_update cannot be given under graph capture")
+            if (not self._ready or not self._clocked or key not in self._many or B not in self._out
+                    or self._ws is None or self._ws.numel() < n_ws):
+                raise ValueError("update_many: call it once eagerly with the same (batch_size, n_updates) before "
+                                 "capturing it")
+        if not self._ready:
+            if len(memory) <= B:
+                raise ValueError(f"update_many: the memory must hold more than batch_size = {B} records")
+            self._ready = True        # a ring never shrinks
+        if self._ws is None or self._ws.numel() < n_ws:
+            self._ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        y = self._out.get(B)
+        if y is None:
+            y = self._out[B] = torch.empty(B, dtype=self.env.dtype, device=dev)
+        with torch.cuda.device(dev):
+            if not self._clocked:
+                self._write_clock()
+                self._clocked = True
+            if first_update is not None:
+                self.clock[0:1].fill_(int(first_update))
+            mb = self._many[key] = memory.sample(B, n_batches=U, out=self._many.get(key))
+            a = _lib.SacUpdatesArgs()
+            a.mode = (_lib.SIT_SAC_UPDATES_WIDE if self.row_pass == "mfma" else
+                      _lib.SIT_SAC_UPDATES_TILED if self.weight_gradient == "mfma" else _lib.SIT_SAC_UPDATES_PLAIN)
+            a.batch, a.n_updates, a.tune, a.seed = B, U, int(self.auto), self.seed & 0xFFFFFFFFFFFFFFFF
+            a.gamma, a.reward_scale, a.target_entropy, a.tau = self.gamma, self.reward_scale, self.target_entropy, self.tau
+            a.target_update_interval, a.workspace_floats = self.target_update_interval, self._ws.numel()
+            a.results_capacity = self._ring.shape[0]
+            a.critic_adam, a.actor_adam = self._clocked_adam("critic"), self._clocked_adam("policy")
+            a.critic_weights, a.critic_m, a.critic_v = (self.online_weights.data_ptr(), self._m["critic"].data_ptr(),
+                                                        self._v["critic"].data_ptr())
+            a.actor_weights, a.actor_m, a.actor_v = (self.actor_weights.data_ptr(), self._m["policy"].data_ptr(),
+                                                     self._v["policy"].data_ptr())
+            a.target_weights, a.alpha = self.target_weights.data_ptr(), self.alpha.data_ptr()
+            if self.auto:
+                a.alpha_adam = self._clocked_adam("alpha")
+                a.log_alpha, a.log_alpha_m, a.log_alpha_v = (self.log_alpha.data_ptr(), self._m["alpha"].data_ptr(),
+                                                             self._v["alpha"].data_ptr())
+            for name in ("state", "action", "reward", "next_state", "mask"):
+                setattr(a, name, self._pointer(name, mb[name]))
+            a.y, a.workspace = y.data_ptr(), self._ws.data_ptr()
+            a.clock, a.results = self.clock.data_ptr(), self._ring.data_ptr()
+            self.env._call("sit_sac_updates", byref(a), self.env._stream())
+        self._clock_dirty = True
+        self._captured = self._captured or capturing
+        touch_parameters(self._params + ([self.log_alpha] if self.auto else []))
+
+    def results(self, last: int | None = None) -> list:
+        """The newest min(last, written, capacity) result rows of ``update_many``'s updates, oldest first, as
+        (critic_1_loss, critic_2_loss, policy_loss, ent_loss, alpha) tuples.  The one call that synchronises."""
+        if self.gradient != "hip":
+            raise ValueError("results needs gradient='hip'")
+        written = int(self.clock[4].item())
+        ring = self._ring.tolist()
+        cap = len(ring)
+        n = min(written, cap) if last is None else max(0, min(int(last), written, cap))
+        return [tuple(ring[(written - n + i) % cap]) for i in range(n)]
 
     def _optim_state_dicts(self) -> dict:
         """The three optimisers' state in ``torch.optim.Adam.state_dict()`` form (both gradient modes write
@@ -569,6 +725,7 @@ class SacLearner(_SacState):
         moment blocks and the step counts, converted), targets (as the packed block, in both modes) and
         log_alpha."""
         tw = self.target_weights if self.target == "hip" else pack_critic_weights(self.target_critic)
+        self._reconcile()
         return {"policy": copy.deepcopy(self.policy.state_dict()), "critic": copy.deepcopy(self.critic.state_dict()),
                 "critic_target": None if tw is None else tw.clone(),
                 "critic_target_state": None if tw is not None else copy.deepcopy(self.target_critic.state_dict()),
@@ -594,6 +751,9 @@ class SacLearner(_SacState):
         self._load_optim_state_dicts(sd["optims"])
         if self.gradient == "hip":
             touch_parameters(self._params)
+            with torch.cuda.device(self.env.device):
+                self._write_clock()        # (the update number is no part of a checkpoint: it stays)
+            self._clock_dirty = self._captured
         elif self.actor_weights is not None:
             pack_actor_weights(self.policy, out=self.actor_weights)
 
@@ -639,5 +799,5 @@ def sac_update_reference(policy: nn.Module, critic: nn.Module, **kw) -> SacUpdat
 
 __all__ = ["QNetwork", "SacLearner", "SacUpdateReference", "pack_critic_weights",
            "unpack_critic_weights", "block_views", "bind_parameters", "touch_parameters", "moments_to_adam_state",
-           "adam_state_to_moments", "sac_noise", "policy_noise", "log_one_minus_tanh_sq", "sac_target_reference", "torch_target",
+           "adam_state_to_moments", "sac_noise", "policy_noise", "adam_scalars_reference", "log_one_minus_tanh_sq", "sac_target_reference", "torch_target",
            "sac_update_reference"]

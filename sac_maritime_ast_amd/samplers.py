@@ -195,6 +195,7 @@ class PolicySampler:
         n, dev, dt = env.n_env, env.device, env.dtype
         self.actor_dtype = actor_dtype or next(policy.parameters()).dtype
         self._w = pack_actor_weights(policy) if fused_actor and self.actor_dtype == torch.float32 else None
+        self._shared = False                  # share_weights: the block is someone else's master copy
         if serve is None:
             serve = "kernel" if self._w is not None and request_capacity is None else "queue"
         if serve not in ("kernel", "queue"):
@@ -239,10 +240,26 @@ class PolicySampler:
         return tuple((p.data_ptr(), p._version) for p in self.policy.parameters())
 
     def refresh_weights(self):
-        """Re-pack the actor weights (after the policy's parameters changed)."""
-        if self._w is not None:
+        """Re-pack the actor weights (after the policy's parameters changed).  Nothing to do after
+        ``share_weights``: the block served from is then the policy's master copy."""
+        if self._w is not None and not self._shared:
             pack_actor_weights(self.policy, out=self._w)
             self._w_version = self._weights_version()
+
+    def share_weights(self, block: torch.Tensor):
+        """Serve from `block`, a packed actor block that someone else keeps current: ``learner.actor_weights`` of
+        a ``SacLearner(gradient="hip")``, the master copy of the policy there.  The sampler's own block is
+        dropped and ``refresh_weights()`` becomes a no-op, so launches need no host step after an update and
+        ``launch(); memory.push(out); learner.update_many(...)`` can be recorded as one HIP graph."""
+        if self._w is None:
+            raise ValueError("share_weights needs the fused actor (the reference's architecture, float32)")
+        if (not isinstance(block, torch.Tensor) or block.dtype != torch.float32 or block.device != self._w.device
+                or block.numel() != _lib.SIT_ACTOR_WEIGHTS or not block.is_contiguous()):
+            raise ValueError(f"share_weights: a contiguous float32 block of {_lib.SIT_ACTOR_WEIGHTS} elements on "
+                             f"{self._w.device} is required")
+        self._w, self._shared = block, True
+        if "actor_weights" in self.io:
+            self.io["actor_weights"] = block
 
     @property
     def env_steps(self) -> torch.Tensor:

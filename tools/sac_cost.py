@@ -5,6 +5,7 @@
     python3 tools/sac_cost.py --gradient [--calls 30] [--warmup 5] [out.json]
     python3 tools/sac_cost.py --weight-gradient [--calls 30] [--warmup 5] [out.json]
     python3 tools/sac_cost.py --rows [--calls 30] [--warmup 5] [out.json]
+    python3 tools/sac_cost.py --clocked [--parent build_diag/libsit_parent.so] [--large] [--order a,b,c,a0] [out.json]
     rocprofv3 --kernel-trace --stats ... -- python3 tools/sac_cost.py --rows --trace valu|mfma
 
 float32 handle of 64 envs, the reference's networks (actor 10-256-256-2, twin critic 11-256-256-1,
@@ -49,7 +50,20 @@ with, per pair, whether the tiled call's min-max range lies wholly below the pla
 with, per pair, whether the wide call's min-max range lies wholly below the narrow call's, and the smallest
 batch from which that holds for all four.  --rows --trace MODE times nothing: it runs `warmup + calls` updates
 at B = 16384 with row_pass=MODE and exits, for a kernel trace of one mode in a run of its own (the
-row-kernel / tile-kernel split of an update: profiles/r12_sac_rows_kernel_stats.csv)."""
+row-kernel / tile-kernel split of an update: profiles/r12_sac_rows_kernel_stats.csv).
+
+--clocked measures ``SacLearner.update_many`` next to ``update_parameters`` (profiles/r13_sac_clock_cost.json): the
+time per update of a span of 8 updates at B = 64, 256 (sum/valu) and 4096 (mfma/valu), with --large also 16384
+(mfma/mfma), from a ring of 32768 records, the variants of one batch size interleaved span by span:
+
+  a    8 update_parameters calls (each reads its results on the host)
+  b    update_many(memory, B, 8), eagerly
+  c    a replay of a HIP graph of update_many(memory, B, 8)
+  a0   the same 8 update_parameters calls on a handle of the parent revision's library (--parent: a library
+       built by `tools/build_variant.py parent --rev <parent>`; without one the variant is left out)
+
+with, per batch size, whether c's whole min-max range lies below a0's and whether a's range overlaps a0's.
+--order sets the order of the variants within a round (a variant's span starts where its predecessor's ended)."""
 import argparse
 import copy
 import json
@@ -73,14 +87,20 @@ def main():
                     help="measure the wide row-kernel calls against the narrow ones (r12_sac_rows_cost.json)")
     ap.add_argument("--trace", choices=("valu", "mfma"), default=None,
                     help="with --rows: only run updates at B = 16384 in this mode, for a profiler's kernel trace")
+    ap.add_argument("--clocked", action="store_true",
+                    help="measure update_many (eager and as a graph) against update_parameters (r13_sac_clock_cost.json)")
+    ap.add_argument("--parent", default=None, help="with --clocked: the parent revision's library (variant a0)")
+    ap.add_argument("--large", action="store_true", help="with --clocked: also B = 16384 with mfma/mfma")
+    ap.add_argument("--order", default="a,b,c,a0", help="with --clocked: the order of the variants within a round")
     ap.add_argument("out", nargs="?", default=None)
     a = ap.parse_args()
     if a.trace and not a.rows:
         ap.error("--trace goes with --rows")
-    if a.gradient + a.weight_gradient + a.rows > 1:
-        ap.error("--gradient, --weight-gradient and --rows are separate measurements")
+    if a.gradient + a.weight_gradient + a.rows + a.clocked > 1:
+        ap.error("--gradient, --weight-gradient, --rows and --clocked are separate measurements")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "r12_sac_rows_cost.json" if a.rows else
+        a.out = os.path.join(ROOT, "profiles", "r13_sac_clock_cost.json" if a.clocked else
+                             "r12_sac_rows_cost.json" if a.rows else
                              "r10_sac_wgrad_cost.json" if a.weight_gradient else
                              "r09_sac_update_cost.json" if a.gradient else "r08_sac_cost.json")
     if a.calls < 20:
@@ -96,11 +116,11 @@ def main():
     torch.manual_seed(0)
     pol0, q0 = GaussianPolicy(), sac.QNetwork()
 
-    def learner(target, gradient="torch", weight_gradient="sum", row_pass="valu"):
+    def learner(target, gradient="torch", weight_gradient="sum", row_pass="valu", env=env):
         return sac.SacLearner(env, copy.deepcopy(pol0).to(dev), critic=copy.deepcopy(q0), target=target, seed=1,
                               gradient=gradient, weight_gradient=weight_gradient, row_pass=row_pass)
 
-    def memory(capacity=4096):
+    def memory(capacity=4096, env=env):
         mem = ReplayMemory(env, capacity, seed=1)
         g = torch.Generator(device=dev).manual_seed(2)
         mem.ring.copy_(torch.randn(mem.ring.shape, generator=g, device=dev))
@@ -135,6 +155,20 @@ def main():
         print(json.dumps(res))
         env.close()
 
+    if a.clocked:
+        env0 = None
+        if a.parent:                               # a second handle, on the parent revision's library
+            ours, path = _lib._lib, _lib.LIB_PATH
+            _lib._lib, _lib.LIB_PATH = None, os.path.abspath(a.parent)
+            try:
+                env0 = VecMultiShipRLEnv(scenario=make_scenario(64), precision=32, device=dev)
+            finally:
+                _lib._lib, _lib.LIB_PATH = ours, path
+            assert env0.lib is not env.lib and not hasattr(env0.lib, "sit_sac_updates")
+        res = clocked(a, torch, env, env0, learner, memory, interleaved)
+        if env0 is not None:
+            env0.close()
+        return finish(res)
     if a.gradient:
         return finish(gradient_half(a, torch, env, _lib, learner, memory, interleaved))
     if a.weight_gradient:
@@ -319,6 +353,53 @@ def row_kernels(a, torch, env, _lib, learner, memory, interleaved):
     holds = [B for B in batches if all(res["batch"][str(B)]["wide_range_below_narrow"].values())]
     from_b = [B for B in batches if all(b in holds for b in batches if b >= B)]
     res["smallest_batch_from_which_all_four_ranges_lie_below"] = from_b[0] if from_b else None
+    return res
+
+
+def clocked(a, torch, env, env0, learner, memory, interleaved):
+    """The --clocked measurement (see the module docstring)."""
+    n, capacity = 8, 32768
+    plan = [(64, "sum", "valu"), (256, "sum", "valu"), (4096, "mfma", "valu")] + ([(16384, "mfma", "mfma")] if a.large else [])
+    res = {"what": "Time per SAC update: 8 update_parameters calls (a; a0 on the parent revision's library) next to "
+                   "update_many(memory, B, 8) eagerly (b) and as a HIP-graph replay (c) (GPU).", "calls": a.calls,
+           "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "ring_records": capacity, "updates_per_span": n,
+           "parent_library": os.path.basename(a.parent) if a.parent else None, "batch": {}}
+    for B, wg, rp in plan:
+        names = ["a", "b", "c"] + (["a0"] if env0 is not None else [])
+        lrn = {k: learner("hip", "hip", wg, rp, env=env0 if k == "a0" else env) for k in names}
+        mems = {k: memory(capacity, env=env0 if k == "a0" else env) for k in names}
+        count = {k: 0 for k in names}
+
+        def by_calls(k):
+            def fn():
+                for _ in range(n):
+                    assert lrn[k].update_parameters(mems[k], B, count[k]) is not None
+                    count[k] += 1
+            return fn
+        lrn["c"].update_many(mems["c"], B, n, first_update=0)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            lrn["c"].update_many(mems["c"], B, n)
+        fns = {"a": by_calls("a"), "b": lambda: lrn["b"].update_many(mems["b"], B, n), "c": graph.replay}
+        if env0 is not None:
+            fns["a0"] = by_calls("a0")
+        r = interleaved({k: fns[k] for k in a.order.split(",") if k in fns})
+        r["order"] = a.order
+        for k in names:
+            r[k] = {f"{stat}_per_update": v / n for stat, v in r[k].items()}
+        assert all(v == v for row in lrn["c"].results(last=n) for v in row)
+        r["mode"] = f"{wg}/{rp}"
+        r["a_over_b_median"] = r["a"]["median_us_per_update"] / r["b"]["median_us_per_update"]
+        r["a_over_c_median"] = r["a"]["median_us_per_update"] / r["c"]["median_us_per_update"]
+        r["c_range_below_a"] = r["c"]["max_us_per_update"] < r["a"]["min_us_per_update"]
+        if env0 is not None:
+            r["a0_over_c_median"] = r["a0"]["median_us_per_update"] / r["c"]["median_us_per_update"]
+            r["c_range_below_a0"] = r["c"]["max_us_per_update"] < r["a0"]["min_us_per_update"]
+            r["a_range_overlaps_a0"] = (r["a"]["min_us_per_update"] <= r["a0"]["max_us_per_update"]
+                                        and r["a0"]["min_us_per_update"] <= r["a"]["max_us_per_update"])
+        res["batch"][str(B)] = r
+        del graph
     return res
 
 
