@@ -508,6 +508,82 @@ int sit_episodes_bytes(const sit_handle* h, size_t* bytes);
 int sit_episodes_get(sit_handle* h, void* dst, void* stream);
 int sit_episodes_set(sit_handle* h, const void* src, void* stream);
 
+/* ---- scores (reduction of the episode records, best episode, conditional weight copy) --
+ * What the reference's driver loop keeps over episodes (test_beds/main_ast.py:432-444: best_reward and
+ * the checkpoint of the policy that reached it; 453-523: avg_reward and the status_record of a scoring
+ * round), reduced on the device from the records above, so that a launch needs no host read.
+ *
+ * The score block is double score[SIT_SCORE_DIM], caller-owned, 8-byte aligned (a checkpoint is that
+ * tensor); integers are stored as exactly representable doubles:
+ *   [0] episodes scored     [1] sum of returns      [2] sum of steps       [3] minimum return
+ *   [4] maximum return      [5] dropped records     [6] updates applied
+ *   [7] 1 if the last update replaced the best episode, else 0
+ *   [8:16] class counts (SIT_SCORE_CLASSES)         [16] stamp of the best episode (sit_score_keep)
+ *   [17:32] zero            [32:64] the best episode's record (the 32 columns above)
+ * sit_score_reset sets everything to zero, then [3] = +inf, [4] = -inf, [16] = NaN, [32:64] = NaN.
+ *
+ * sit_score_update reduces the records a sit_episodes_update left in (records, record_count).  With
+ * count = max(*record_count, 0) and m = min(count, record_capacity), both read on the device:
+ *  - SIT_SCORE_FRESH resets the block first;
+ *  - record j < m is included iff episode_limit == 0 or rec[1] < episode_limit (a scoring round takes
+ *    the first episode_limit episodes of every env);
+ *  - [0] += included records, [2] += their steps, [6] += 1;
+ *  - class c += included records with (class_any[c] == 0 || status & class_any[c]) and
+ *    !(status & class_none[c]); a class whose masks are both 0 is unused and stays 0;
+ *  - the round's return sum is formed in a fixed order, so its bits never depend on scheduling: x[j] = ret
+ *    of an included record, +0.0 otherwise; chunks of 256 slots, zero-padded; in each chunk the halving
+ *    tree x[i] += x[i + s] for s = 128, 64, ..., 1; the chunk sums go in groups of 256 (zero-padded)
+ *    through the same tree; the group sums are added to a running value that starts at +0.0, in
+ *    ascending order; finally [1] = [1] + round sum;
+ *  - [3] = min([3], the included non-NaN returns) + 0.0 and [4] = max(...) + 0.0 (a zero result is +0.0);
+ *  - the round's best is the included record with the greatest non-NaN return, the lowest slot among
+ *    equal returns; it replaces the block's best iff the block has none ([35] is NaN) or its return is
+ *    strictly greater: then its 32 columns go to [32:64] and [7] = 1; otherwise [7] = 0;
+ *  - SIT_SCORE_CONSUME: [5] += count - m, then *record_count = 0, so the log holds only what arrived
+ *    since the last score.  Without the flag nothing of the log is written, and scoring the same buffer
+ *    twice counts its records twice.
+ * Two launches on the caller's stream (one block per chunk of record_capacity, since the host never
+ * knows m: a block past m reads the count and exits; then one block).  The per-chunk scratch belongs
+ * to the handle and is freed by sit_destroy; sit_score_reserve allocates it for buffers of up to
+ * max_records records, and an update that needs more grows it, which allocates and cannot be captured
+ * (the contract of sit_replay_reserve).  After a sufficient reserve an update allocates nothing, never
+ * synchronises and can be captured in a HIP graph.  Arguments are validated before any launch
+ * (SIT_E_INVALID).
+ *
+ * sit_score_keep: when score[7] != 0 it copies every src[i] to dst[i] (floats[i] float32 each) and
+ * sets score[16] = (double)*stamp if stamp is given; otherwise it writes nothing.  One launch; the
+ * decision is read from the block on the device, so "update, keep" keeps the weights that produced the
+ * best episode without a host step.  Blocks must not overlap. */
+#define SIT_SCORE_DIM 64
+#define SIT_SCORE_CLASSES 8
+#define SIT_SCORE_KEEP_BLOCKS 4
+#define SIT_SCORE_CONSUME 1u  /* count the dropped records and empty the log */
+#define SIT_SCORE_FRESH 2u    /* reset the block before the update */
+typedef struct sit_score_args {
+  int32_t record_capacity;  /* rows of records, > 0 */
+  uint32_t flags;           /* SIT_SCORE_* */
+  int64_t episode_limit;    /* >= 0; 0: no limit */
+  const double* records;    /* double[record_capacity][32] */
+  int64_t* record_count;    /* int64[1], 8-byte aligned; written with SIT_SCORE_CONSUME only */
+  double* score;            /* double[SIT_SCORE_DIM], 8-byte aligned */
+  uint32_t class_any[SIT_SCORE_CLASSES];
+  uint32_t class_none[SIT_SCORE_CLASSES];
+} sit_score_args;
+typedef struct sit_score_keep_args {
+  int32_t n_blocks;                          /* 0 .. SIT_SCORE_KEEP_BLOCKS */
+  const float* src[SIT_SCORE_KEEP_BLOCKS];   /* 16-byte aligned */
+  float* dst[SIT_SCORE_KEEP_BLOCKS];         /* 16-byte aligned */
+  int64_t floats[SIT_SCORE_KEEP_BLOCKS];     /* > 0, at most 2^34 */
+  double* score;                             /* double[SIT_SCORE_DIM], 8-byte aligned */
+  const int64_t* stamp;                      /* int64[1], 8-byte aligned, or NULL */
+} sit_score_keep_args;
+size_t sit_score_args_size(void);
+size_t sit_score_keep_args_size(void);
+int sit_score_reset(sit_handle* h, double* score, void* stream);
+int sit_score_reserve(sit_handle* h, int32_t max_records);
+int sit_score_update(sit_handle* h, const sit_score_args* a, void* stream);
+int sit_score_keep(sit_handle* h, const sit_score_keep_args* a, void* stream);
+
 /* ---- replay memory (device-side ring and minibatches) -------------------------------
  * What the reference's driver loop does with its ReplayMemory (test_beds/main_ast.py:350-396:
  * memory.push per sampling event, len(memory), memory.sample for agent.update_parameters), on the

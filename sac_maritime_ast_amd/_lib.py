@@ -30,6 +30,8 @@ SIT_SAC_CLOCK_WORDS = 64       # int64 words of the device-side update clock (si
 SIT_SAC_UPDATES_PLAIN, SIT_SAC_UPDATES_TILED, SIT_SAC_UPDATES_WIDE = 0, 1, 2
 SIT_LOG_KEYS, SIT_LOG_ROWS = 27, 62
 SIT_EPISODE_ACTIONS, SIT_EPISODE_DIM = 14, 32
+SIT_SCORE_DIM, SIT_SCORE_CLASSES, SIT_SCORE_KEEP_BLOCKS = 64, 8, 4
+SIT_SCORE_CONSUME, SIT_SCORE_FRESH = 1, 2
 INIT_FIELDS = ("north", "east", "yaw", "surge", "sway", "yaw_rate", "shaft_speed", "desired_speed",
                "ship_speed_i", "shaft_speed_i")
 
@@ -102,6 +104,21 @@ class EpisodesArgs(ctypes.Structure):
         ("n_steps", c_int32), ("record_capacity", c_int32), ("env_id_offset", c_int64),
         ("reward", c_void_p), ("done", c_void_p), ("status", c_void_p), ("action_out", c_void_p),
         ("next_state", c_void_p), ("records", c_void_p), ("record_count", c_void_p), ("status_hist", c_void_p),
+    ]
+
+
+class ScoreArgs(ctypes.Structure):
+    _fields_ = [
+        ("record_capacity", c_int32), ("flags", ctypes.c_uint32), ("episode_limit", c_int64),
+        ("records", c_void_p), ("record_count", c_void_p), ("score", c_void_p),
+        ("class_any", ctypes.c_uint32 * SIT_SCORE_CLASSES), ("class_none", ctypes.c_uint32 * SIT_SCORE_CLASSES),
+    ]
+
+
+class ScoreKeepArgs(ctypes.Structure):
+    _fields_ = [
+        ("n_blocks", c_int32), ("src", c_void_p * SIT_SCORE_KEEP_BLOCKS), ("dst", c_void_p * SIT_SCORE_KEEP_BLOCKS),
+        ("floats", c_int64 * SIT_SCORE_KEEP_BLOCKS), ("score", c_void_p), ("stamp", c_void_p),
     ]
 
 
@@ -215,6 +232,12 @@ SIGNATURES = {
     "sit_episodes_bytes": (c_int32, [c_void_p, POINTER(c_size_t)]),
     "sit_episodes_get": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "sit_episodes_set": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "sit_score_args_size": (c_size_t, []),
+    "sit_score_keep_args_size": (c_size_t, []),
+    "sit_score_reset": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "sit_score_reserve": (c_int32, [c_void_p, c_int32]),
+    "sit_score_update": (c_int32, [c_void_p, POINTER(ScoreArgs), c_void_p]),
+    "sit_score_keep": (c_int32, [c_void_p, POINTER(ScoreKeepArgs), c_void_p]),
     "sit_replay_push_args_size": (c_size_t, []),
     "sit_replay_sample_args_size": (c_size_t, []),
     "sit_replay_reserve": (c_int32, [c_void_p, c_int32, c_void_p]),
@@ -268,6 +291,7 @@ def load():
         raise ImportError(f"sit_episodes_args layout mismatch: C {lib.sit_episodes_args_size()} vs "
                           f"ctypes {ctypes.sizeof(EpisodesArgs)} bytes")
     for fn, struct in (("sit_replay_push_args_size", ReplayPushArgs), ("sit_replay_sample_args_size", ReplaySampleArgs),
+                       ("sit_score_args_size", ScoreArgs), ("sit_score_keep_args_size", ScoreKeepArgs),
                        ("sit_sac_target_args_size", SacTargetArgs),
                        ("sit_sac_critic_step_args_size", SacCriticStepArgs),
                        ("sit_sac_policy_step_args_size", SacPolicyStepArgs),

@@ -46,6 +46,8 @@ struct sit_handle {
   size_t replay_temp = 0;               //   bytes of the sort's temporary storage
   size_t replay_asked = 0;              //   the last size query: items and the bytes hipcub asked for
   size_t replay_answer = 0;
+  unsigned char* score = nullptr;       // sit_score_update: one ScPart per chunk of 256 record slots (sit_score.h)
+  size_t score_chunks = 0;              //   chunks the scratch holds
 };
 
 namespace {

@@ -6,6 +6,7 @@
 #include "sit_map_build.h"
 #include "sit_actor.h"
 #include "sit_episodes.h"
+#include "sit_score.h"
 #include "sit_replay.h"
 #include "sit_sac.h"
 #include "sit_sac_grad.h"
@@ -311,6 +312,7 @@ void sit_destroy(sit_handle* h) {
   if (h->map) (void)setup_free(h->map);
   if (h->episodes) (void)setup_free(h->episodes);
   if (h->replay) (void)setup_free(h->replay);
+  if (h->score) (void)setup_free(h->score);
 #ifndef SIT_HOST_MEMORY_TEST
   if (h->stage) (void)hipHostFree(h->stage);
 #endif
@@ -696,6 +698,34 @@ int sit_episodes_set(sit_handle* h, const void* src, void* stream) {
   if (rc) return rc;
   HIP_TRY(h, hipMemcpyAsync(h->episodes, src, ep_layout(h).blob_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SIT_OK;
+}
+
+// ---- scores (sit_score.h) --------------------------------------------------------------------
+size_t sit_score_args_size(void) { return sizeof(sit_score_args); }
+size_t sit_score_keep_args_size(void) { return sizeof(sit_score_keep_args); }
+
+int sit_score_reset(sit_handle* h, double* score, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = score_block_error(score)) return fail(h, SIT_E_INVALID, "%s", why);
+  return score_launch_reset(h, score, (hipStream_t)stream);
+}
+
+int sit_score_reserve(sit_handle* h, int32_t max_records) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = score_reserve_args_error(max_records)) return fail(h, SIT_E_INVALID, "%s (got %d)", why, max_records);
+  return score_reserve(h, (size_t)max_records);
+}
+
+int sit_score_update(sit_handle* h, const sit_score_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = score_update_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return score_launch_update(h, a, (hipStream_t)stream);
+}
+
+int sit_score_keep(sit_handle* h, const sit_score_keep_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = score_keep_args_error(a)) return fail(h, SIT_E_INVALID, "%s", why);
+  return score_launch_keep(h, a, (hipStream_t)stream);
 }
 
 // ---- replay memory (sit_replay.h) ----------------------------------------------------------

@@ -141,6 +141,21 @@ def pack_actor_weights(policy: nn.Module, out: torch.Tensor | None = None) -> to
         return out
 
 
+def unpack_actor_weights(block: torch.Tensor, policy: nn.Module) -> nn.Module:
+    """The inverse of ``pack_actor_weights``: copy a packed actor block (e.g. one kept by
+    ``Scoreboard.keep``) into the parameters of `policy`, a GaussianPolicy of the reference's architecture.
+    Returns `policy`."""
+    if pack_actor_weights(policy) is None:
+        raise ValueError("unpack_actor_weights: policy must have the reference's architecture (10 -> 256 -> 256 -> 2)")
+    if not isinstance(block, torch.Tensor) or block.dtype != torch.float32 or block.numel() != _lib.SIT_ACTOR_WEIGHTS:
+        raise ValueError(f"unpack_actor_weights: block must be a float32 tensor of {_lib.SIT_ACTOR_WEIGHTS} elements")
+    l1, _, l2, _, l3 = policy.net
+    with torch.no_grad():
+        for layer, name, seg in block_segments(block.detach().reshape(-1), _lib.SIT_OBS_DIM, 2):
+            getattr((l1, l2, l3)[layer], name).copy_(seg)
+    return policy
+
+
 def _trunk(net: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """net(x) for an nn.Sequential trunk, each Linear followed by a ReLU evaluated as one GEMM with
     the bias and the ReLU in its epilogue (torch._addmm_activation: hipBLASLt's fused epilogue on ROCm)
