@@ -4,8 +4,11 @@ use (route rows, waypoint index, route length, spatial-index entries, edge ids, 
 mixed-cell records), and the in-kernel serving pass its published row count, served env ids and
 LDS extents.  The workload of every kernel variant runs under it with no check failing; a
 deliberately corrupted waypoint index and route length are reported (and clamped, so nothing is read
-out of bounds).  The debug library runs in a child process (SIT_LIBRARY) so that this test session
-keeps the release library."""
+out of bounds).  A second child runs the maps of tests/map_cases.py, which reach every path of the spatial
+index (full scans, band scans, long candidate lists, 32 rings, images beyond the LDS budgets): their probe
+points, and fused and single steps on the maps that change the step kernels' dispatch, in both precisions.
+The debug library runs in a child process (SIT_LIBRARY) so that this test session keeps the release
+library."""
 import json
 import os
 import subprocess
@@ -99,3 +102,55 @@ def test_debug_variant_checks_every_kernel():
         assert res[f"f{prec}_served"] > 0, res
     assert res["bad_waypoint"] & (1 << 1), res          # kDbgWaypoint
     assert res["bad_route_len"] & (1 << 2), res         # kDbgRouteLen
+
+
+MAP_WORKLOAD = r'''
+import json, os, sys
+import numpy as np
+import torch
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import map_cases as mc
+from sac_maritime_ast_amd import VecMultiShipRLEnv, _lib, make_scenario
+from sac_maritime_ast_amd.scenario import Scenario
+lib = _lib.load()
+flags = _lib.ctypes.c_uint32()
+def read():
+    torch.cuda.synchronize()
+    _lib.check(lib.sit_debug_flags(_lib.ctypes.byref(flags)))
+    return int(flags.value)
+res = {"debug_build": int(lib.sit_debug_build()), "flags": {}, "kernels": {}}
+read()
+for name in mc.MAPS:
+    sc = make_scenario(128, cap=32)
+    sc = Scenario(sc.routes, sc.n_wpt, sc.init, list(mc.load(name)))
+    pts = mc.probe_points(name)
+    for prec in (64, 32):
+        env = VecMultiShipRLEnv(scenario=sc, precision=prec, device="cuda:0")
+        env.probe_map(torch.from_numpy(pts if prec == 64 else pts.astype(np.float32)))
+        res["flags"][f"{name}_f{prec}_probe"] = read()
+        if name in mc.STEP_MAPS:
+            env.reset(); env.init_step()
+            env.rollout(100, seed=25450)
+            kernels = [lib.sit_step_kernel(env.handle).decode()]
+            for _ in range(5):
+                env.rollout(1, seed=25450)
+            kernels.append(lib.sit_step_kernel(env.handle).decode())
+            res["kernels"][f"{name}_f{prec}"] = kernels
+            res["flags"][f"{name}_f{prec}_steps"] = read()
+print(json.dumps(res))
+'''
+
+
+def test_debug_variant_checks_every_map_path():
+    if not os.path.exists(DEBUG_LIB):
+        pytest.fail("libsit_debug.so is missing: __graft_entry__.build() builds it")
+    env = dict(os.environ, SIT_LIBRARY=DEBUG_LIB)
+    p = subprocess.run([sys.executable, "-c", MAP_WORKLOAD, ROOT], env=env, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    res = json.loads(p.stdout.strip().splitlines()[-1])
+    print("debug variant on the maps:", res)
+    assert res["debug_build"] == 1
+    assert len(res["flags"]) == 2 * (12 + 4) and len(res["kernels"]) == 2 * 4
+    failed = {k: f"{v:#x}" for k, v in res["flags"].items() if v != 0}
+    assert not failed, f"bounds checks failed: {failed}"

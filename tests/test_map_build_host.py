@@ -23,7 +23,14 @@ sit_kernels.hip was compiled alone at -O3 with -DSIT_HOST_MEMORY_TEST and no san
 through SIT_LIBRARY and ctypes (sit_create, sit_load_map, sit_map_info for "lds_bytes") on a
 machine without a GPU.  That commit accepted all four maps (use_index = use_cells = 1 for each).
 The sanitizer build at -O1 and the -O3 library agree because the baseline x86-64 target has no
-fused multiply-add: nothing contracts."""
+fused multiply-add: nothing contracts.
+
+The maps of tests/map_cases.py (NEW_MAPS; its docstring: which limit of the index format each one reaches) run
+through the same program.  No older build recorded them, so there is no image hash: the flags and counts
+must equal the table the GPU tests rely on (map_cases.expected), and the image must be sound in itself --
+every candidate, band and live entry an edge id below n_vert, every group pointer and band range inside the
+n_idx entries of the index, every mixed-cell record's span inside the n_live entries, frank the prefix
+popcount of the class words."""
 import functools
 import hashlib
 import json
@@ -34,6 +41,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import map_cases as mc
 from helpers import GOLDEN, POLYS, ROOT
 
 MAPS = ("scenario", "triangle", "repeated_vertex", "gon256")
@@ -122,3 +130,72 @@ def test_maps_reach_the_paths_the_scenario_never_takes(program):
     meta, image = _built(program, "repeated_vertex")[8]
     edges = np.frombuffer(image, dtype=np.float64, count=6 * meta["n_vert"]).reshape(-1, 6)   # Edge<double>: 48 bytes
     assert np.array_equal(edges[1, :2], edges[1, 2:4]) and edges[1, 4] == 0.0 and np.all(np.delete(edges[:, 4], 1) > 0)
+
+
+@pytest.mark.parametrize("real_size", [4, 8])
+@pytest.mark.parametrize("name", mc.NEW_MAPS)
+def test_new_maps_reach_their_paths_with_sound_images(program, name, real_size):
+    meta, image = _built(program, name)[real_size]
+    want = mc.expected(name, real_size)
+    assert {k: meta[k] for k in want} == want
+    assert len(image) == meta["size"] and meta["map_bytes"] <= meta["ring_off"] <= meta["bbox_off"] <= meta["size"]
+    nv, n_idx, n_mixed, n_live = meta["n_vert"], meta["n_idx"], meta["n_mixed"], meta["n_live"]
+    esz = 48 if real_size == 8 else 32          # Edge<T>: five reals and the polygon id, 16-byte aligned
+    real = np.float32 if real_size == 4 else np.float64
+    edges = np.frombuffer(image, dtype=np.uint8, count=nv * esz).reshape(nv, esz)
+    poly = edges[:, 5 * real_size:5 * real_size + 4].copy().view(np.uint32).ravel()
+    offs, verts = _map_file(name)
+    assert np.array_equal(poly, np.repeat(np.arange(meta["n_poly"]), np.diff(offs)))
+    assert np.array_equal(edges[:, :2 * real_size].copy().view(real).reshape(nv, 2), verts.astype(real))
+    idx = np.frombuffer(image, dtype=np.uint16, count=n_idx, offset=meta["idx_off"]).astype(np.int64)
+    if meta["use_index"]:
+        rec = idx[:mc.K_BAND_BASE].reshape(-1, 4)
+        first_ids = np.stack([rec[:, 0] & 0xff, rec[:, 0] >> 8, rec[:, 1] & 0xff, rec[:, 1] >> 8, rec[:, 2] & 0xff], 1)
+        assert first_ids.max() < nv
+        more, ptr = rec[:, 2] >> 8, rec[:, 3]
+        starts = idx[mc.K_BAND_BASE:mc.K_IDX_HEAD]
+        assert starts[0] == mc.K_IDX_HEAD and (np.diff(starts) >= 0).all() and starts[-1] <= n_idx
+        gbase = (starts[-1] + 3) & ~3
+        assert idx[mc.K_IDX_HEAD:starts[-1]].max() < nv                        # band entries: edge ids
+        assert (4 * ptr >= gbase).all() and (4 * (ptr + more) <= n_idx).all()     # further groups: inside idx
+        assert 4 * (ptr + more).max() == n_idx and (n_idx - gbase) == 4 * more.sum()
+        grp = idx[gbase:].reshape(-1, 4)
+        if len(grp):                                                              # 5 u8 ids in 8 bytes
+            assert max((grp[:, :2] >> 8).max(), (grp[:, :3] & 0xff).max()) < nv
+            assert not grp[:, 3].any() and not (grp[:, 2] >> 8).any()
+    else:
+        assert n_idx == 4 and not idx.any()                                       # the placeholder pf_cell reads
+    fine = np.frombuffer(image, dtype=np.uint32, count=mc.K_FINE * mc.K_FINE // 16, offset=meta["fine_off"])
+    cls = (fine[:, None] >> (2 * np.arange(16, dtype=np.uint32))[None, :]) & 3    # [word, cell in word]
+    assert cls.max() == 2 and int((cls == 2).sum()) == n_mixed
+    if meta["use_cells"]:
+        assert n_mixed <= 65535 and n_live <= 65535
+        frank = np.frombuffer(image, dtype=np.uint16, count=len(fine), offset=meta["frank_off"])
+        per_word = (cls == 2).sum(axis=1)
+        assert np.array_equal(frank, np.concatenate([[0], np.cumsum(per_word)[:-1]]))
+        crec = np.frombuffer(image, dtype=np.uint32, count=2 * n_mixed, offset=meta["crec_off"]).reshape(-1, 2)
+        first, cnt = (crec[:, 1] & 0xffff).astype(np.int64), (crec[:, 1] >> 16).astype(np.int64)
+        assert (first + cnt <= n_live).all() and first[0] == 0 and np.array_equal(first[1:], np.cumsum(cnt)[:-1] & 0xffff)
+        assert not (crec[:, 0] >> np.uint32(meta["n_poly"] - 1) >> np.uint32(1)).any()   # parity bits of real rings only
+        clive = np.frombuffer(image, dtype=np.uint8, count=n_live, offset=meta["clive_off"])
+        assert int(clive.max()) < nv
+        assert meta["clive_off"] + n_live <= meta["map_bytes"]
+    else:
+        assert meta["frank_off"] <= meta["crec_off"] == meta["clive_off"] <= meta["map_bytes"] < meta["frank_off"] + 256 + 8
+
+
+def test_new_maps_set_what_they_are_for(program):
+    """Parity bit 31 in squares32's records; tens of further groups in comb_dense; negative grid origins in
+    shifted; a clockwise ring in nested."""
+    meta, image = _built(program, "squares32")[8]
+    crec = np.frombuffer(image, dtype=np.uint32, count=2 * meta["n_mixed"], offset=meta["crec_off"]).reshape(-1, 2)
+    assert (crec[:, 0] >> np.uint32(31)).any()
+    meta, image = _built(program, "comb_dense")[8]
+    idx = np.frombuffer(image, dtype=np.uint16, count=meta["n_idx"], offset=meta["idx_off"])
+    assert (idx[2:mc.K_BAND_BASE:4] >> 8).max() >= 20
+    meta, _ = _built(program, "shifted")[8]
+    assert max(float.fromhex(meta[k]) for k in ("gx0", "gy0", "fx0", "fy0", "by0", "max_e", "max_n")) < 0
+
+    def area(r):
+        return 0.5 * float(np.sum(r[:, 0] * np.roll(r[:, 1], -1) - np.roll(r[:, 0], -1) * r[:, 1]))
+    assert [area(r) > 0 for r in mc.load("nested")] == [True, True, True, False]
