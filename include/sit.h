@@ -654,6 +654,10 @@ size_t sit_replay_sample_args_size(void);
 int sit_replay_reserve(sit_handle* h, int32_t max_src_capacity, void* stream);
 int sit_replay_push(sit_handle* h, const sit_replay_push_args* a, void* stream);
 int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream);
+/* sit_replay_sample with the state and next_state columns normalised by `affine` (float[SIT_OBSNORM_AFFINE],
+ * "observation normalisation" below) as they are copied: the bits of sit_replay_sample followed by
+ * sit_obsnorm_apply on state and next_state.  Every other output is sit_replay_sample's. */
+int sit_replay_sample_normalised(sit_handle* h, const sit_replay_sample_args* a, const float* affine, void* stream);
 
 /* ---- SAC learner: the no-gradient half of an update ----------------------------------
  * agent.update_parameters (test_beds/main_ast.py:350-362; twin Q networks of hidden size 256,
@@ -916,6 +920,56 @@ typedef struct sit_sac_updates_args {
 size_t sit_sac_updates_args_size(void);
 int sit_sac_updates(sit_handle* h, const sit_sac_updates_args* a, void* stream);
 int sit_sac_adam_scalars(sit_handle* h, const sit_sac_adam* o, int64_t t0, int32_t n, float* out, void* stream);
+
+/* ---- observation normalisation (running statistics, the affine, the folded actor block) ----
+ * Per-column x^_i = (x_i - shift_i) * scale_i over the ten observation columns, applied where minibatches
+ * are drawn (sit_replay_sample_normalised, sit_obsnorm_apply) and where the actor is served (sit_obsnorm_fold
+ * writes a serving block whose first layer absorbs the affine); no step kernel and no learner kernel knows
+ * of it.  x^ is never clipped: a clip cannot be folded into W1.  Outliers are bounded by min_std instead.
+ * Two caller-owned device tensors, so a checkpoint is those two:
+ *   block   double[SIT_OBSNORM_DIM], 8-byte aligned: 0 n (records accounted), 1 updates applied, 2 seen (the
+ *           replay cursor's `pushed` up to which records are accounted), 3 records overwritten in the ring
+ *           before they were seen, 8:18 mean, 24:34 M2 (sum of squared deviations), the rest zero
+ *   affine  float[SIT_OBSNORM_AFFINE], 16-byte aligned: 0:10 shift, 16:26 scale, 32:42 min_std, the rest zero
+ * sit_obsnorm_reset: block zero, shift 0, scale 1, min_std from the host array of ten floats (NULL: zeros).
+ *
+ * sit_obsnorm_update accounts the records of a replay ring that are new since the last update; everything
+ * is decided on the device.  With pushed = cursor[0]:
+ *   start = max(seen, pushed - capacity);  m = min(pushed - start, max_new)   (m < 0 counts as 0)
+ *   the new records are logical indices g in [start, start + m), ring row g mod capacity, ascending g
+ *   per column c < 10 of those rows, as float64:  S = tree sum of x;  mean_b = S / m;
+ *     Q = tree sum of (x - mean_b)^2      (the tree of the scores' return sum above: chunks of 256 through
+ *     the zero-padded halving tree, chunk sums in groups of 256 through the same tree, groups ascending)
+ *   n' = n + m;  d = mean_b - mean;  mean' = mean + d (m / n');  M2' = (M2 + Q) + (d d) ((n m) / n')
+ *   s = sqrt(M2' / n');  std = s > min_std ? s : min_std;  scale = (float)(1 / std);  shift = (float)mean'
+ *   word 3 += start - seen;  seen = start + m;  n = n';  word 1 += 1
+ * in IEEE double in this order without contraction.  A remainder beyond max_new is picked up by the next
+ * update; m = 0 writes nothing but word 1.  Four launches (chunk sums, batch mean, chunk deviations, finish)
+ * sized by max_new; their scratch belongs to the handle and is allocated by sit_obsnorm_reserve only: an
+ * update with max_new beyond the reserve fails.  No block waits on another.
+ *
+ * sit_obsnorm_apply: x^ = (x - (real)shift) * (real)scale in the handle's real type, two roundings, in place
+ * over rows_a and, when given, rows_b (real[n_rows][10], 2-real aligned).  NaN passes.
+ * sit_obsnorm_fold: dst = src (float[SIT_ACTOR_WEIGHTS], 16-byte aligned, not overlapping) except
+ *   W1'[j][i] = W1[j][i] * scale[i] in float32;  b1'[j] = (float)((double)b1[j] - sum_i (double)W1'[j][i] *
+ *   (double)shift[i]), i ascending from +0.0
+ * so that actor(dst, x) = actor(src, x^).  The identity affine gives src's bits. */
+#define SIT_OBSNORM_DIM 64
+#define SIT_OBSNORM_AFFINE 48
+typedef struct sit_obsnorm_args {
+  int32_t capacity;         /* ring records, > 0 */
+  int32_t max_new;          /* most records accounted by this update, > 0 and within the reserve */
+  const void* ring;         /* real[capacity][24], 4-real aligned */
+  const int64_t* cursor;    /* the replay cursor, int64[4] */
+  double* block;            /* double[SIT_OBSNORM_DIM] */
+  float* affine;            /* float[SIT_OBSNORM_AFFINE] */
+} sit_obsnorm_args;
+size_t sit_obsnorm_args_size(void);
+int sit_obsnorm_reset(sit_handle* h, double* block, float* affine, const float* min_std, void* stream);
+int sit_obsnorm_reserve(sit_handle* h, int32_t max_new);
+int sit_obsnorm_update(sit_handle* h, const sit_obsnorm_args* a, void* stream);
+int sit_obsnorm_apply(sit_handle* h, const float* affine, void* rows_a, void* rows_b, int64_t n_rows, void* stream);
+int sit_obsnorm_fold(sit_handle* h, const float* affine, const float* src, float* dst, void* stream);
 
 #ifdef __cplusplus
 }

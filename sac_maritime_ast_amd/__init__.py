@@ -7,10 +7,12 @@ from .status import status_string
 from .episodes import EpisodeLog, episodes_reference
 from .replay import ReplayMemory, replay_reference
 from .score import REFERENCE_CLASSES, Scoreboard, Scorer, score_reference
+from .obsnorm import REFERENCE_OBS_HIGH, REFERENCE_OBS_LOW, ObsNormalizer, ObsNormReference
 
 __all__ = ["params", "params_from_reference", "Scenario", "make_scenario", "status_string",
            "VecMultiShipRLEnv", "MultiShipRLEnv", "load_library", "EpisodeLog", "episodes_reference",
-           "ReplayMemory", "replay_reference", "REFERENCE_CLASSES", "Scoreboard", "Scorer", "score_reference", "QNetwork", "SacLearner", "SacUpdateReference",
+           "ReplayMemory", "replay_reference", "REFERENCE_CLASSES", "Scoreboard", "Scorer", "score_reference",
+           "ObsNormalizer", "ObsNormReference", "REFERENCE_OBS_LOW", "REFERENCE_OBS_HIGH", "QNetwork", "SacLearner", "SacUpdateReference",
            "pack_critic_weights", "unpack_critic_weights", "sac_noise", "policy_noise", "sac_target_reference",
            "sac_update_reference", "bind_parameters", "block_views", "moments_to_adam_state", "adam_state_to_moments"]
 # the learner's names (sac.py imports torch: resolved on first use, like the env classes)

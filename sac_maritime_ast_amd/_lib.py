@@ -32,6 +32,7 @@ SIT_LOG_KEYS, SIT_LOG_ROWS = 27, 62
 SIT_EPISODE_ACTIONS, SIT_EPISODE_DIM = 14, 32
 SIT_SCORE_DIM, SIT_SCORE_CLASSES, SIT_SCORE_KEEP_BLOCKS = 64, 8, 4
 SIT_SCORE_CONSUME, SIT_SCORE_FRESH = 1, 2
+SIT_OBSNORM_DIM, SIT_OBSNORM_AFFINE = 64, 48
 INIT_FIELDS = ("north", "east", "yaw", "surge", "sway", "yaw_rate", "shaft_speed", "desired_speed",
                "ship_speed_i", "shaft_speed_i")
 
@@ -183,6 +184,13 @@ class SacUpdatesArgs(ctypes.Structure):
     ]
 
 
+class ObsnormArgs(ctypes.Structure):
+    _fields_ = [
+        ("capacity", c_int32), ("max_new", c_int32), ("ring", c_void_p), ("cursor", c_void_p), ("block", c_void_p),
+        ("affine", c_void_p),
+    ]
+
+
 class SitError(RuntimeError):
     pass
 
@@ -243,6 +251,7 @@ SIGNATURES = {
     "sit_replay_reserve": (c_int32, [c_void_p, c_int32, c_void_p]),
     "sit_replay_push": (c_int32, [c_void_p, POINTER(ReplayPushArgs), c_void_p]),
     "sit_replay_sample": (c_int32, [c_void_p, POINTER(ReplaySampleArgs), c_void_p]),
+    "sit_replay_sample_normalised": (c_int32, [c_void_p, POINTER(ReplaySampleArgs), c_void_p, c_void_p]),
     "sit_sac_target_args_size": (c_size_t, []),
     "sit_sac_target": (c_int32, [c_void_p, POINTER(SacTargetArgs), c_void_p]),
     "sit_sac_polyak": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p]),
@@ -259,6 +268,12 @@ SIGNATURES = {
     "sit_sac_updates_args_size": (c_size_t, []),
     "sit_sac_updates": (c_int32, [c_void_p, POINTER(SacUpdatesArgs), c_void_p]),
     "sit_sac_adam_scalars": (c_int32, [c_void_p, POINTER(SacAdam), c_int64, c_int32, c_void_p, c_void_p]),
+    "sit_obsnorm_args_size": (c_size_t, []),
+    "sit_obsnorm_reset": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sit_obsnorm_reserve": (c_int32, [c_void_p, c_int32]),
+    "sit_obsnorm_update": (c_int32, [c_void_p, POINTER(ObsnormArgs), c_void_p]),
+    "sit_obsnorm_apply": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sit_obsnorm_fold": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -295,7 +310,7 @@ def load():
                        ("sit_sac_target_args_size", SacTargetArgs),
                        ("sit_sac_critic_step_args_size", SacCriticStepArgs),
                        ("sit_sac_policy_step_args_size", SacPolicyStepArgs),
-                       ("sit_sac_updates_args_size", SacUpdatesArgs)):
+                       ("sit_sac_updates_args_size", SacUpdatesArgs), ("sit_obsnorm_args_size", ObsnormArgs)):
         if hasattr(lib, fn) and getattr(lib, fn)() != ctypes.sizeof(struct):
             raise ImportError(f"{fn[:-5]} layout mismatch: C {getattr(lib, fn)()} vs ctypes {ctypes.sizeof(struct)} bytes")
     _lib = lib

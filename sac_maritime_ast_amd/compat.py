@@ -43,6 +43,7 @@ from . import _lib
 from .config import params as default_params
 from .config import params_from_reference
 from .env import LO_FIELDS, VecMultiShipRLEnv
+from .obsnorm import REFERENCE_OBS_HIGH, REFERENCE_OBS_LOW
 from .scenario import Scenario, polygons
 from .status import status_string
 from .trajectory import LOG_KEYS, REWARD_SERIES
@@ -500,9 +501,7 @@ class MultiShipRLEnv:
         self._step_fn = self.vec.lib.sit_step_host
         r = scenario.routes[0, 1]
         nw = int(scenario.n_wpt[0, 1])
-        self.observation_space = _Box(
-            np.array([0, 0, -np.pi, -3000, 0, 0, 0, 0, -np.pi, 0], dtype=np.float32),
-            np.array([10000, 20000, np.pi, 3000, 1000, 2000, 10000, 20000, np.pi, 1000], dtype=np.float32))
+        self.observation_space = _Box(REFERENCE_OBS_LOW.copy(), REFERENCE_OBS_HIGH.copy())
         self.action_space = _Box(np.array([-np.pi / 6], dtype=np.float32), np.array([np.pi / 6], dtype=np.float32))
         self.np_random = np.random.default_rng()
         # the construction-time observation (MSRL_Env.py:88-92): float32, from the live pose

@@ -48,6 +48,8 @@ struct sit_handle {
   size_t replay_answer = 0;
   unsigned char* score = nullptr;       // sit_score_update: one ScPart per chunk of 256 record slots (sit_score.h)
   size_t score_chunks = 0;              //   chunks the scratch holds
+  unsigned char* obsnorm = nullptr;     // sit_obsnorm_update: mean_b and two sums per chunk of 256 records (sit_obsnorm.h)
+  size_t obsnorm_records = 0;           //   records the scratch was reserved for
 };
 
 namespace {

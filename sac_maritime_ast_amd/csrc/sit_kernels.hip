@@ -7,6 +7,7 @@
 #include "sit_actor.h"
 #include "sit_episodes.h"
 #include "sit_score.h"
+#include "sit_obsnorm.h"
 #include "sit_replay.h"
 #include "sit_sac.h"
 #include "sit_sac_grad.h"
@@ -313,6 +314,7 @@ void sit_destroy(sit_handle* h) {
   if (h->episodes) (void)setup_free(h->episodes);
   if (h->replay) (void)setup_free(h->replay);
   if (h->score) (void)setup_free(h->score);
+  if (h->obsnorm) (void)setup_free(h->obsnorm);
 #ifndef SIT_HOST_MEMORY_TEST
   if (h->stage) (void)hipHostFree(h->stage);
 #endif
@@ -755,8 +757,8 @@ int sit_replay_push(sit_handle* h, const sit_replay_push_args* a, void* stream) 
   return with_real(h, [&](auto t) { return replay_launch_push<decltype(t)>(h, a, (hipStream_t)stream); });
 }
 
-int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream) {
-  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+// affine: NULL for sit_replay_sample, the affine of sit_replay_sample_normalised
+static int replay_sample(sit_handle* h, const sit_replay_sample_args* a, const float* affine, void* stream) {
   if (!a) return fail(h, SIT_E_INVALID, "replay: null args");
   if (a->capacity <= 0) return fail(h, SIT_E_INVALID, "replay: capacity must be positive (got %d)", a->capacity);
   if (a->batch <= 0) return fail(h, SIT_E_INVALID, "replay: batch must be positive (got %d)", a->batch);
@@ -769,7 +771,18 @@ int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stre
     return fail(h, SIT_E_INVALID, "replay: every output (state, action, reward, next_state, mask, env, index) is required");
   const size_t quad = 4 * real_size(h);
   if ((uintptr_t)a->ring % quad) return fail(h, SIT_E_INVALID, "replay: ring must be aligned to 4 reals (%zu bytes)", quad);
-  return with_real(h, [&](auto t) { return replay_launch_sample<decltype(t)>(h, a, (hipStream_t)stream); });
+  return with_real(h, [&](auto t) { return replay_launch_sample<decltype(t)>(h, a, (hipStream_t)stream, affine); });
+}
+
+int sit_replay_sample(sit_handle* h, const sit_replay_sample_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  return replay_sample(h, a, nullptr, stream);
+}
+
+int sit_replay_sample_normalised(sit_handle* h, const sit_replay_sample_args* a, const float* affine, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = obsnorm_affine_error(affine)) return fail(h, SIT_E_INVALID, "%s", why);
+  return replay_sample(h, a, affine, stream);
 }
 
 // ---- SAC learner (sit_sac.h) ---------------------------------------------------------------
@@ -850,6 +863,43 @@ int sit_sac_adam_scalars(sit_handle* h, const sit_sac_adam* o, int64_t t0, int32
   if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
   if (const char* why = sac_adam_scalars_args_error(o, t0, n, out)) return fail(h, SIT_E_INVALID, "%s", why);
   return sac_launch_adam_scalars(h, o, t0, n, out, (hipStream_t)stream);
+}
+
+// ---- observation normalisation (sit_obsnorm.h) -------------------------------------------------
+size_t sit_obsnorm_args_size(void) { return sizeof(sit_obsnorm_args); }
+
+int sit_obsnorm_reset(sit_handle* h, double* block, float* affine, const float* min_std, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = obsnorm_reset_args_error(block, affine, min_std)) return fail(h, SIT_E_INVALID, "%s", why);
+  return obsnorm_launch_reset(h, block, affine, min_std, (hipStream_t)stream);
+}
+
+int sit_obsnorm_reserve(sit_handle* h, int32_t max_new) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = obsnorm_reserve_args_error(max_new)) return fail(h, SIT_E_INVALID, "%s (got %d)", why, max_new);
+  return obsnorm_reserve(h, (size_t)max_new);
+}
+
+int sit_obsnorm_update(sit_handle* h, const sit_obsnorm_args* a, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = obsnorm_update_args_error(a, real_size(h), (int64_t)h->obsnorm_records))
+    return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) { return obsnorm_launch_update<decltype(t)>(h, a, (hipStream_t)stream); });
+}
+
+int sit_obsnorm_apply(sit_handle* h, const float* affine, void* rows_a, void* rows_b, int64_t n_rows, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = obsnorm_apply_args_error(affine, rows_a, rows_b, n_rows, real_size(h)))
+    return fail(h, SIT_E_INVALID, "%s", why);
+  return with_real(h, [&](auto t) {
+    return obsnorm_launch_apply<decltype(t)>(h, affine, rows_a, rows_b, n_rows, (hipStream_t)stream);
+  });
+}
+
+int sit_obsnorm_fold(sit_handle* h, const float* affine, const float* src, float* dst, void* stream) {
+  if (!h) return fail(nullptr, SIT_E_INVALID, "null handle");
+  if (const char* why = obsnorm_fold_args_error(affine, src, dst)) return fail(h, SIT_E_INVALID, "%s", why);
+  return obsnorm_launch_fold(h, affine, src, dst, (hipStream_t)stream);
 }
 
 }  // extern "C"

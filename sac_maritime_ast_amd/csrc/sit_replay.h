@@ -14,6 +14,8 @@
 //   k_replay_pushed   one thread: pushed += n, dropped += count - n
 // Sample:
 //   k_replay_gather   one lane per (u, b): the keyed permutation, then the record split into the outputs
+//                     (kNorm: state and next_state through the affine of sit_obsnorm.h as they are copied;
+//                     sit_replay_sample_normalised only)
 //   k_replay_drawn    one thread: draws += n_batches
 //
 // Included from sit_kernels.hip only (the strictly compiled translation unit).  Records and sampled
@@ -24,6 +26,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "sit_host.h"
+#include "sit_obsnorm.h"
 
 namespace {
 
@@ -119,9 +122,10 @@ struct RpSample {
   uint64_t seed;
   R *state, *action, *reward, *next_state, *mask;
   int32_t *env, *index;
+  const float* affine;   // kNorm only
 };
 
-template <typename R>
+template <typename R, bool kNorm>
 __global__ __launch_bounds__(kRpBlock) void k_replay_gather(RpSample<R> a) {
   const long long t = (long long)blockIdx.x * kRpBlock + threadIdx.x;
   if (t >= (long long)a.batch * a.n_batches) return;
@@ -145,10 +149,19 @@ __global__ __launch_bounds__(kRpBlock) void k_replay_gather(RpSample<R> a) {
     const double id = (double)rec.r[SIT_TRANSITION_DIM - 1];
     env = id >= 0.0 && id < 2147483648.0 ? (int32_t)id : -1;
   }
+  if (kNorm) {
 #pragma unroll
-  for (int j = 0; j < SIT_OBS_DIM; ++j) {
-    a.state[t * SIT_OBS_DIM + j] = rec.r[j];
-    a.next_state[t * SIT_OBS_DIM + j] = rec.r[SIT_OBS_DIM + 2 + j];
+    for (int j = 0; j < SIT_OBS_DIM; ++j) {
+      const R shift = (R)a.affine[kOnShift + j], scale = (R)a.affine[kOnScale + j];
+      a.state[t * SIT_OBS_DIM + j] = obsnorm_apply<R>(rec.r[j], shift, scale);
+      a.next_state[t * SIT_OBS_DIM + j] = obsnorm_apply<R>(rec.r[SIT_OBS_DIM + 2 + j], shift, scale);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < SIT_OBS_DIM; ++j) {
+      a.state[t * SIT_OBS_DIM + j] = rec.r[j];
+      a.next_state[t * SIT_OBS_DIM + j] = rec.r[SIT_OBS_DIM + 2 + j];
+    }
   }
   a.action[t] = rec.r[SIT_OBS_DIM];
   a.reward[t] = rec.r[SIT_OBS_DIM + 1];
@@ -231,10 +244,11 @@ int replay_launch_push(sit_handle* h, const sit_replay_push_args* a, hipStream_t
 #endif
 }
 
+// affine: NULL for the plain gather, else the normalised one (sit_replay_sample_normalised)
 template <typename R>
-int replay_launch_sample(sit_handle* h, const sit_replay_sample_args* a, hipStream_t s) {
+int replay_launch_sample(sit_handle* h, const sit_replay_sample_args* a, hipStream_t s, const float* affine = nullptr) {
 #ifdef SIT_HOST_MEMORY_TEST
-  (void)a; (void)s;
+  (void)a; (void)s; (void)affine;
   return fail(h, SIT_E_STATE, "replay: no device in the host-memory test build");
 #else
   RpSample<R> g{};
@@ -251,8 +265,13 @@ int replay_launch_sample(sit_handle* h, const sit_replay_sample_args* a, hipStre
   g.mask = (R*)a->mask;
   g.env = a->env;
   g.index = a->index;
+  g.affine = affine;
   const long long lanes = (long long)a->batch * a->n_batches;
-  hipLaunchKernelGGL(k_replay_gather<R>, dim3((unsigned)((lanes + kRpBlock - 1) / kRpBlock)), dim3(kRpBlock), 0, s, g);
+  const dim3 grid((unsigned)((lanes + kRpBlock - 1) / kRpBlock));
+  if (affine)
+    hipLaunchKernelGGL((k_replay_gather<R, true>), grid, dim3(kRpBlock), 0, s, g);
+  else
+    hipLaunchKernelGGL((k_replay_gather<R, false>), grid, dim3(kRpBlock), 0, s, g);
   hipLaunchKernelGGL(k_replay_drawn, dim3(1), dim3(1), 0, s, reinterpret_cast<long long*>(a->cursor), a->n_batches);
   HIP_TRY(h, hipGetLastError());
   return SIT_OK;

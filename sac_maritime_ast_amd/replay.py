@@ -115,7 +115,8 @@ class ReplayReference:
         self.cursor[0] += n
         self.cursor[1] += count - n
 
-    def sample(self, batch: int, n_batches: int = 1) -> dict:
+    def sample(self, batch: int, n_batches: int = 1, normalizer=None) -> dict:
+        """normalizer: an ``ObsNormReference`` applied to state and next_state (sample, then apply)."""
         B, U = int(batch), int(n_batches)
         if B <= 0 or U <= 0:
             raise ValueError("batch and n_batches must be positive")
@@ -134,6 +135,8 @@ class ReplayReference:
                    "next_state": rec[..., OBS + 2:2 * OBS + 2].copy(), "mask": rec[..., DIM - 2].copy(),
                    "env": env_ids(rec[..., DIM - 1]), "index": idx.astype(np.int32)}
         self.cursor[2] += U
+        if normalizer is not None:
+            normalizer.apply(out["state"], out["next_state"])
         return out
 
 
@@ -196,13 +199,21 @@ class ReplayMemory:
         with self._device():
             self.env._call("sit_replay_push", byref(a), self.env._stream())
 
-    def sample(self, batch: int, n_batches: int = 1, out: dict | None = None) -> dict:
+    def sample(self, batch: int, n_batches: int = 1, out: dict | None = None, normalizer=None) -> dict:
         """`n_batches` minibatches of `batch` records: state [U, B, 10], action [U, B, 1], reward [U, B],
         next_state [U, B, 10], mask [U, B], env int32 [U, B], index int32 [U, B] (the ring row; -1 and
-        zeros from an empty ring).  Tensors of `out` with the right shape and type are reused."""
+        zeros from an empty ring).  Tensors of `out` with the right shape and type are reused.
+        normalizer: an ``ObsNormalizer`` of the same device; state and next_state then leave the gather
+        normalised by its current affine (``sit_replay_sample_normalised``; the bits of sample + normalize)."""
         import torch
         B, U = int(batch), int(n_batches)
         dt, dev = self.env.dtype, self.ring.device
+        affine = None
+        if normalizer is not None:
+            affine = getattr(normalizer, "affine", None)
+            if (not isinstance(affine, torch.Tensor) or affine.device != dev or affine.dtype != torch.float32
+                    or affine.numel() != _lib.SIT_OBSNORM_AFFINE or not affine.is_contiguous()):
+                raise ValueError(f"normalizer: an ObsNormalizer on {dev} is required")
         shapes = {"state": ((U, B, OBS), dt), "action": ((U, B, 1), dt), "reward": ((U, B), dt),
                   "next_state": ((U, B, OBS), dt), "mask": ((U, B), dt), "env": ((U, B), torch.int32),
                   "index": ((U, B), torch.int32)}
@@ -219,7 +230,10 @@ class ReplayMemory:
             t = out.get(k)
             setattr(a, k, None if t is None else t.data_ptr())
         with self._device():
-            self.env._call("sit_replay_sample", byref(a), self.env._stream())
+            if affine is None:
+                self.env._call("sit_replay_sample", byref(a), self.env._stream())
+            else:
+                self.env._call("sit_replay_sample_normalised", byref(a), affine.data_ptr(), self.env._stream())
         return out
 
     def _cursor(self):

@@ -33,8 +33,14 @@ with ``PolicySampler.share_weights`` a whole "rollout, push, n updates" iteratio
 those of the same number of ``update_parameters`` calls; ``adam_scalars_reference`` is the specification of the
 clock's Adam scalars.
 
+``SacLearner(..., obs_norm=norm)`` (an ``obsnorm.ObsNormalizer``): every minibatch is drawn normalised
+(``ReplayMemory.sample(normalizer=norm)``), and every update call ends by folding ``actor_weights`` into
+``serving_weights`` on the stream (``sit_obsnorm_fold``), the block the samplers serve from; no learner kernel
+changes.  ``SacUpdateReference(obs_norm=ObsNormReference)`` normalises its float64 batches with the same float32
+affine values.
+
 Not included: HIP gradients for other architectures, prioritised replay, n-step returns,
-observation normalisation, multi-rank learners, hyper-parameter schedules inside a graph, a device-side gate
+multi-rank learners, hyper-parameter schedules inside a graph, a device-side gate
 on len(memory).
 """
 from __future__ import annotations
@@ -310,9 +316,9 @@ def torch_target(policy, target_critic, next_state, reward, mask, eps, alpha, ga
         return {"y": y, "next_action": a, "next_logp": logp, "q1": q1, "q2": q2}
 
 
-def _sample(memory, batch_size):
+def _sample(memory, batch_size, normalizer=None):
     """One minibatch of a ReplayMemory (device tensors) or a ReplayReference (NumPy) as [B, ...] items."""
-    b = memory.sample(batch_size)
+    b = memory.sample(batch_size) if normalizer is None else memory.sample(batch_size, normalizer=normalizer)
     return {k: b[k][0] for k in ("state", "action", "reward", "next_state", "mask")}
 
 
@@ -405,13 +411,19 @@ class SacLearner(_SacState):
     results_written); the five results of each go to a ring of `results_capacity` rows that ``results()``
     reads.  ``update_parameters``, ``update_many``, graph replays, ``state_dict`` and ``load_state_dict`` may be
     mixed freely: the clock's step words are the master copy once ``update_many`` has run, and the host's
-    counts are reconciled with them (one read) where they are needed."""
+    counts are reconciled with them (one read) where they are needed.
+
+    obs_norm (an ``ObsNormalizer`` of the same env): ``update_parameters`` (all modes) and ``update_many`` draw
+    normalised minibatches, and each ends by folding ``actor_weights`` into ``serving_weights`` on the stream, so
+    the fold is part of a captured ``update_many``; serve with ``sampler.share_weights(learner.serving_weights)``.
+    Update the normaliser after the push and before the learner's call: the minibatches and the fold then use
+    one affine.  ``state_dict`` is unchanged; the normaliser checkpoints itself."""
 
     def __init__(self, env, policy: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
                  alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
                  reward_scale: float = 1.0, seed: int = 25450, target: str = "hip", critic: nn.Module | None = None,
                  gradient: str = "torch", weight_gradient: str = "sum", row_pass: str = "valu",
-                 results_capacity: int = 1024):
+                 results_capacity: int = 1024, obs_norm=None):
         if target not in ("hip", "torch"):
             raise ValueError("target must be 'hip' or 'torch'")
         if gradient not in ("hip", "torch"):
@@ -437,6 +449,11 @@ class SacLearner(_SacState):
                     reward_scale=reward_scale, seed=seed)
         self._ready = False
         self._out = {}
+        self.obs_norm, self._serving = obs_norm, None
+        if obs_norm is not None:
+            affine = getattr(obs_norm, "affine", None)
+            if getattr(obs_norm, "env", None) is not env or not isinstance(affine, torch.Tensor):
+                raise ValueError("obs_norm: an ObsNormalizer of the learner's env is required")
         if target == "hip":
             self.actor_weights = pack_actor_weights(policy)
             self.online_weights = pack_critic_weights(self.critic)
@@ -472,6 +489,23 @@ class SacLearner(_SacState):
             self._clocked = False         # update_many has run: the clock's step words are the master copy
             self._clock_dirty = False     # clocked work since the host's counts were last reconciled
             self._captured = False        # an update_many was captured: replays advance the clock unseen
+        if obs_norm is not None:
+            if self.actor_weights is None:
+                raise ValueError("obs_norm needs the reference's actor (10 -> 256 -> 256 -> 2): its block is folded")
+            self._serving = torch.empty_like(self.actor_weights)
+            self._fold()
+
+    @property
+    def serving_weights(self) -> torch.Tensor:
+        """The packed block the samplers serve with a normaliser: ``actor_weights`` with the affine folded into
+        its first layer, rewritten at the end of every update call."""
+        if self._serving is None:
+            raise ValueError("serving_weights needs obs_norm; without a normaliser serve actor_weights")
+        return self._serving
+
+    def _fold(self):
+        if self._serving is not None:
+            self.obs_norm.fold(self.actor_weights, self._serving)
 
     # ---------------- the no-gradient half ----------------
     def td_target(self, next_state, reward, mask, update: int, noise=None, diagnostics: dict | None = None):
@@ -529,7 +563,7 @@ class SacLearner(_SacState):
             if len(memory) <= B:
                 return None
             self._ready = True        # a ring never shrinks
-        raw = _sample(memory, B)
+        raw = _sample(memory, B, self.obs_norm)
         if self.gradient == "hip":
             return self._hip_update(raw, B, updates)
         if self.target == "hip":
@@ -549,6 +583,7 @@ class SacLearner(_SacState):
             self._polyak()
         if self.actor_weights is not None:
             pack_actor_weights(self.policy, out=self.actor_weights)
+        self._fold()
         return tuple(torch.stack([l1, l2, lp, la.reshape(()), self.alpha[0]]).tolist())
 
     # ---------------- one update, gradient="hip" ----------------
@@ -595,6 +630,7 @@ class SacLearner(_SacState):
             if updates % self.target_update_interval == 0:
                 self.env._call("sit_sac_polyak", c_void_p(self.target_weights.data_ptr()),
                                c_void_p(self.online_weights.data_ptr()), self.online_weights.numel(), self.tau, stream)
+        self._fold()
         touch_parameters(self._params + ([self.log_alpha] if self.auto else []))
         self._next_update = int(updates) + 1
         if self._clocked:
@@ -661,7 +697,10 @@ class SacLearner(_SacState):
                 self._clocked = True
             if first_update is not None:
                 self.clock[0:1].fill_(int(first_update))
-            mb = self._many[key] = memory.sample(B, n_batches=U, out=self._many.get(key))
+            if self.obs_norm is None:
+                mb = self._many[key] = memory.sample(B, n_batches=U, out=self._many.get(key))
+            else:
+                mb = self._many[key] = memory.sample(B, n_batches=U, out=self._many.get(key), normalizer=self.obs_norm)
             a = _lib.SacUpdatesArgs()
             a.mode = (_lib.SIT_SAC_UPDATES_WIDE if self.row_pass == "mfma" else
                       _lib.SIT_SAC_UPDATES_TILED if self.weight_gradient == "mfma" else _lib.SIT_SAC_UPDATES_PLAIN)
@@ -684,6 +723,7 @@ class SacLearner(_SacState):
             a.y, a.workspace = y.data_ptr(), self._ws.data_ptr()
             a.clock, a.results = self.clock.data_ptr(), self._ring.data_ptr()
             self.env._call("sit_sac_updates", byref(a), self.env._stream())
+            self._fold()
         self._clock_dirty = True
         self._captured = self._captured or capturing
         touch_parameters(self._params + ([self.log_alpha] if self.auto else []))
@@ -764,7 +804,8 @@ class SacUpdateReference(_SacState):
 
     def __init__(self, policy: nn.Module, critic: nn.Module, *, gamma: float = 0.99, tau: float = 0.005, lr: float = 3e-4,
                  alpha: float = 0.2, automatic_entropy_tuning: bool = True, target_update_interval: int = 1,
-                 reward_scale: float = 1.0, seed: int = 25450):
+                 reward_scale: float = 1.0, seed: int = 25450, obs_norm=None):
+        self.obs_norm = obs_norm          # an ObsNormReference: its float32 affine's values, applied in float64
         self.policy = copy.deepcopy(policy).to(device="cpu", dtype=torch.float64)
         self.critic = copy.deepcopy(critic).to(device="cpu", dtype=torch.float64)
         self.target_critic = copy.deepcopy(self.critic).requires_grad_(False)
@@ -778,6 +819,9 @@ class SacUpdateReference(_SacState):
             return None
         as64 = lambda v: (v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))).to(torch.float64)  # noqa: E731
         batch = {k: as64(v) for k, v in _sample(memory, B).items()}
+        if self.obs_norm is not None:
+            for k in ("state", "next_state"):
+                batch[k] = torch.from_numpy(self.obs_norm.normalized(batch[k].numpy(), np.float64))
         eps = torch.from_numpy(sac_noise(self.seed, np.arange(B), updates))
         y = torch_target(self.policy, self.target_critic, batch["next_state"], batch["reward"], batch["mask"], eps,
                          self.alpha, self.gamma, self.reward_scale)["y"]

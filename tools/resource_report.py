@@ -49,7 +49,7 @@ def report(src, flags):
                 v = v.strip()
                 kernels[cur][FIELDS[k.strip()]] = int(v) if v.lstrip("-").isdigit() else v
     names = list(kernels)
-    return {d: kernels[n] for n, d in zip(names, demangle(names)) if "k_env_steps" in d or "k_policy" in d or "k_episodes" in d or "k_replay" in d or "k_sac" in d}
+    return {d: kernels[n] for n, d in zip(names, demangle(names)) if "k_env_steps" in d or "k_policy" in d or "k_episodes" in d or "k_replay" in d or "k_sac" in d or "k_obsnorm" in d}
 
 
 def main():
